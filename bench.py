@@ -8,6 +8,12 @@ aggregate samples/sec over all ranks.
 Launch (single GPU):   python bench.py --steps 50 --warmup 10
 Launch (N GPUs): python -m torch.distributed.run --nnodes=1 \
     --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
+
+A plain run sets up, warms up, times --steps steps and prints one JSON
+result line. --dump-outputs DIR also writes a timed step's loss and logits
+as DIR/<name>.npy (the inputs are seeded, so two builds can be compared
+output for output; see the option's help for which step). Anything the benchmark measures beyond the
+headline figure belongs behind --full (nothing today).
 """
 import argparse
 import json
@@ -17,6 +23,51 @@ import time
 import torch
 
 DLRM_BASELINE_SAMPLES_SEC = 141266.06  # DeepRec DLRM FP32+BF16
+DUMP_MAX_BYTES = 64 << 20  # --dump-outputs budget over all arrays
+
+
+def _dump_outputs(directory, outputs, rank):
+    """Write each output as <name>.npy (float32); ranks above 0 add a
+    _rank<r> suffix. An output over its share of the budget is cut to a
+    fixed, seeded sample of its elements."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    per_array = DUMP_MAX_BYTES // max(len(outputs), 1) // 4
+    for name, t in outputs.items():
+        a = t.detach().to("cpu", torch.float32).numpy()
+        if a.size > per_array:
+            idx = np.random.default_rng(0).choice(a.size, per_array,
+                                                  replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        suffix = f"_rank{rank}" if rank else ""
+        np.save(os.path.join(directory, f"{name}{suffix}.npy"), a)
+
+
+def _snapshot_device_state(device):
+    """Byte copies of every live tensor storage on `device`, as
+    (view, copy) pairs; _restore_device_state writes them back in place.
+    A captured step reads and writes device memory only, so this is all
+    the state a replay depends on."""
+    import gc
+    seen, snap = set(), []
+    for o in gc.get_objects():
+        if type(o) not in (torch.Tensor, torch.nn.Parameter):
+            continue
+        if o.device != device:
+            continue
+        st = o.untyped_storage()
+        if st.nbytes() == 0 or st.data_ptr() in seen:
+            continue
+        seen.add(st.data_ptr())
+        view = torch.empty(0, dtype=torch.uint8, device=device).set_(st)
+        snap.append((view, view.clone()))
+    return snap
+
+
+def _restore_device_state(snap):
+    with torch.no_grad():
+        for view, saved in snap:
+            view.copy_(saved)
 
 
 def main():
@@ -38,7 +89,22 @@ def main():
                         "even at WORLD_SIZE=1 — exercises the exact "
                         "nccl/RCCL call pattern of a full node on a "
                         "single-GPU lease")
+    p.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                   help="after the timed steps, write the loss and logits "
+                        "a timed step returned as DIR/<name>.npy (float32): "
+                        "the third training step, computed again from "
+                        "saved state by the captured graph, in a captured "
+                        "single-GPU run (its training steps do not repeat "
+                        "bit for bit); the last timed step otherwise. Inputs are seeded, so two "
+                        "builds can be compared output for output")
+    p.add_argument("--full", action="store_true",
+                   help="also run whatever the benchmark measures beyond "
+                        "its headline figure (nothing today: a plain run "
+                        "already does only set-up, warm-up, the timed "
+                        "steps and the result line)")
     args = p.parse_args()
+    if args.steps < 1:
+        p.error("--steps must be at least 1")
 
     world_size = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -121,16 +187,31 @@ def main():
     n_total = args.warmup + args.steps
     batches = [ds.next_batch() for _ in range(min(n_total, 20))]
 
+    # what the most recent step handed back to its caller (--dump-outputs).
+    # Detached: a live reference to an eager step's loss keeps its autograd
+    # graph (and AccumulateGrad nodes bound to the default stream) alive
+    # into the capture below, whose backward then runs on another stream.
+    last = {}
+
     def eager_step(i):
         dense, sparse, labels = batches[i % len(batches)]
         logits = model(dense, sparse)
         loss = model.loss_fn(logits, labels)
+        last["loss"], last["logits"] = loss.detach(), logits.detach()
         opt.zero_grad()
         loss.backward()
         if reducer is not None:
             reducer.allreduce(async_op=True)
         opt.step()
         return loss
+
+    # The bf16 step sums weight gradients with fp32 atomics, so a training
+    # run never repeats bit for bit and the difference grows with every
+    # step. A captured single-GPU run therefore dumps a step that depends
+    # on neither --steps nor --warmup: its third training step, computed
+    # after the timed region by the captured graph from the device state
+    # saved here after the second (capture needs two eager steps).
+    snap = None
 
     one_step = eager_step
     if use_graph:
@@ -173,12 +254,16 @@ def main():
             coll.graph_mode = True
             for i in range(max(args.warmup, 2)):
                 eager_step(i)
+                if i == 1 and args.dump_outputs:
+                    torch.cuda.synchronize()
+                    snap = _snapshot_device_state(device)
             torch.cuda.synchronize()
         # static input buffers + whole-step capture (the distributed step
         # records its RCCL all-to-alls/all-reduce into the same graph —
         # shapes are static via the padded exchange)
         sdense, sids, slabels = (t.clone() for t in batches[0])
         graph = torch.cuda.CUDAGraph()
+        last.clear()
         opt.zero_grad()
         with torch.cuda.graph(graph):
             logits = model(sdense, sids)
@@ -188,6 +273,8 @@ def main():
                 reducer.allreduce(async_op=True)
             opt.step()
         torch.cuda.synchronize()
+        # replays write the step's results into these static tensors
+        last["loss"], last["logits"] = loss.detach(), logits.detach()
         if rank == 0:
             print("bench: hipGraph capture ok", flush=True)
 
@@ -264,6 +351,14 @@ def main():
     global_batch = args.batch * n_gpus
     samples_per_sec = global_batch * args.steps / elapsed
     ms_per_step = elapsed / args.steps * 1000.0
+
+    if args.dump_outputs:
+        if snap is not None and use_graph:
+            _restore_device_state(snap)
+            one_step(2)
+            torch.cuda.synchronize()
+            model.collection.storage._check_error()
+        _dump_outputs(args.dump_outputs, last, rank)
 
     out_json = None
     if rank == 0:
