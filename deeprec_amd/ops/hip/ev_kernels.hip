@@ -60,6 +60,83 @@ DEV_INLINE __hip_bfloat16 f2bf(float v) { return __float2bfloat16(v); }
 // hash probe / insert
 // ---------------------------------------------------------------------
 
+// Read-only linear probe: the entry index of `key`, or -1 when the probe
+// reaches EMPTY_KEY (valid early exit: eviction compacts, no tombstones)
+// or has wrapped the whole table.
+DEV_INLINE int64_t ht_find(const int64_t* __restrict__ ht_keys,
+                           int64_t cap_mask, int64_t key) {
+  uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
+  for (int64_t probe = 0; probe <= cap_mask; ++probe) {
+    int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
+    int64_t cur = ht_keys[idx];
+    if (cur == key) return idx;
+    if (cur == EMPTY_KEY) return -1;
+  }
+  return -1;
+}
+
+// Find `key` or claim (CAS) the first empty entry on its probe path; a
+// fresh claim bumps entry_counter. Returns the entry index, or -1 when the
+// table is full (host sizing bug: the caller raises error 2).
+DEV_INLINE int64_t ht_find_or_claim(int64_t* __restrict__ ht_keys,
+                                    int64_t cap_mask, int64_t key,
+                                    int32_t* __restrict__ entry_counter) {
+  uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
+  for (int64_t probe = 0; probe <= cap_mask; ++probe) {
+    int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
+    int64_t cur = ht_keys[idx];
+    if (cur != key) {
+      if (cur != EMPTY_KEY) continue;
+      int64_t prev = (int64_t)atomicCAS(
+          (unsigned long long*)&ht_keys[idx],
+          (unsigned long long)EMPTY_KEY, (unsigned long long)key);
+      if (prev != EMPTY_KEY && prev != key) continue;  // lost race
+      if (prev == EMPTY_KEY) atomicAdd(entry_counter, 1);
+    }
+    return idx;
+  }
+  return -1;
+}
+
+// Row of default_values that initializes `key`. Composite keys
+// (EmbeddingCollection): table * dvd + (raw_key % dvd); key_bits == 0
+// means plain keys.
+DEV_INLINE int64_t default_row(int64_t key, int key_bits,
+                               int default_value_dim) {
+  if (key_bits > 0) {
+    int64_t mask = ((int64_t)1 << key_bits) - 1;
+    return (key >> key_bits) * default_value_dim +
+           (int64_t)((uint64_t)(key & mask) % (uint64_t)default_value_dim);
+  }
+  return (int64_t)((uint64_t)key % (uint64_t)default_value_dim);
+}
+
+// Admit entry idx: grant a value slot and initialize its row from
+// default_values. Returns the slot, or -1 with error 1 when the slab is
+// out of space (host must grow).
+DEV_INLINE int32_t ht_admit(
+    int64_t key, int64_t idx, int32_t* __restrict__ ht_slot,
+    int32_t* __restrict__ slot_counter, int max_slots,
+    float* __restrict__ values, const float* __restrict__ default_values,
+    int dim, int default_value_dim, int key_bits, int init_limit,
+    int32_t* __restrict__ error_flag) {
+  int32_t slot = atomicAdd(slot_counter, 1);
+  if (slot >= max_slots) {
+    atomicExch(error_flag, 1);
+    return -1;
+  }
+  ht_slot[idx] = slot;
+  // multi-tier (HBM_DRAM): rows at slot >= init_limit live in the host
+  // cold slab; the host initializes those (kernel must not touch them)
+  if (slot < init_limit) {
+    const float* src =
+        default_values + default_row(key, key_bits, default_value_dim) * dim;
+    float* dst = values + (int64_t)slot * dim;
+    for (int d = 0; d < dim; ++d) dst[d] = src[d];
+  }
+  return slot;
+}
+
 // Lookup-or-insert for a batch of UNIQUE keys. Per key:
 //   - find or claim (CAS) a hash entry
 //   - freq += count; version = step (no atomics needed: keys unique)
@@ -83,64 +160,27 @@ __global__ void k_lookup_insert(
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t gstride = gridDim.x * (int64_t)blockDim.x;
   for (; i < n; i += gstride) {
-  const int64_t key = keys[i];
-  uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-  int32_t slot = -1;
-  for (int64_t probe = 0; probe <= cap_mask; ++probe) {
-    int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-    int64_t cur = ht_keys[idx];
-    if (cur != key) {
-      if (cur != EMPTY_KEY) continue;
-      if (!train) { out_slots[i] = -1; goto done_i; }
-      int64_t prev = (int64_t)atomicCAS(
-          (unsigned long long*)&ht_keys[idx],
-          (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-      if (prev != EMPTY_KEY && prev != key) continue;  // lost race
-      if (prev == EMPTY_KEY) atomicAdd(entry_counter, 1);
-    }
-    // found or claimed entry idx
-    int32_t freq = ht_freq[idx];
-    if (train) {
-      freq += (counts ? counts[i] : 1);
-      ht_freq[idx] = freq;
-      ht_version[idx] = step;
-    }
-    slot = ht_slot[idx];
-    if (slot < 0 && train && freq >= filter_freq) {
-      slot = atomicAdd(slot_counter, 1);
-      if (slot >= max_slots) {  // out of slab space: host must grow
-        atomicExch(error_flag, 1);
-        out_slots[i] = -1;
-        goto done_i;
-      }
-      ht_slot[idx] = slot;
-      // multi-tier (HBM_DRAM): rows at slot >= init_limit live in the host
-      // cold slab; the host initializes those (kernel must not touch them)
-      if (slot >= init_limit) {
-        out_slots[i] = slot;
-        goto done_i;
-      }
-      // composite keys (EmbeddingCollection): default row is
-      // table * dvd + (raw_key % dvd); key_bits == 0 means plain keys
-      int64_t dvrow;
-      if (key_bits > 0) {
-        int64_t mask = ((int64_t)1 << key_bits) - 1;
-        dvrow = (key >> key_bits) * default_value_dim +
-                (int64_t)((uint64_t)(key & mask) %
-                          (uint64_t)default_value_dim);
+    const int64_t key = keys[i];
+    int32_t slot = -1;
+    if (!train) {
+      int64_t idx = ht_find(ht_keys, cap_mask, key);
+      if (idx >= 0) slot = ht_slot[idx];
+    } else {
+      int64_t idx = ht_find_or_claim(ht_keys, cap_mask, key, entry_counter);
+      if (idx < 0) {
+        atomicExch(error_flag, 2);  // table full (host sizing bug)
       } else {
-        dvrow = (int64_t)((uint64_t)key % (uint64_t)default_value_dim);
+        int32_t freq = ht_freq[idx] + (counts ? counts[i] : 1);
+        ht_freq[idx] = freq;
+        ht_version[idx] = step;
+        slot = ht_slot[idx];
+        if (slot < 0 && freq >= filter_freq)
+          slot = ht_admit(key, idx, ht_slot, slot_counter, max_slots, values,
+                          default_values, dim, default_value_dim, key_bits,
+                          init_limit, error_flag);
       }
-      const float* src = default_values + dvrow * dim;
-      float* dst = values + (int64_t)slot * dim;
-      for (int d = 0; d < dim; ++d) dst[d] = src[d];
     }
     out_slots[i] = slot;
-    goto done_i;
-  }
-  atomicExch(error_flag, 2);  // table full (host sizing bug)
-  out_slots[i] = -1;
-  done_i:;
   }
 }
 
@@ -156,26 +196,14 @@ __global__ void k_insert_bulk(
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t gstride = gridDim.x * (int64_t)blockDim.x;
   for (; i < n; i += gstride) {
-    const int64_t key = keys[i];
-    uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-    bool placed = false;
-    for (int64_t probe = 0; probe <= cap_mask && !placed; ++probe) {
-      int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-      int64_t cur = ht_keys[idx];
-      if (cur != key) {
-        if (cur != EMPTY_KEY) continue;
-        int64_t prev = (int64_t)atomicCAS(
-            (unsigned long long*)&ht_keys[idx],
-            (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-        if (prev != EMPTY_KEY && prev != key) continue;
-        if (prev == EMPTY_KEY) atomicAdd(entry_counter, 1);
-      }
-      ht_slot[idx] = slots[i];
-      if (freqs) ht_freq[idx] = freqs[i];
-      if (versions) ht_version[idx] = versions[i];
-      placed = true;
+    int64_t idx = ht_find_or_claim(ht_keys, cap_mask, keys[i], entry_counter);
+    if (idx < 0) {
+      atomicExch(error_flag, 2);
+      continue;
     }
-    if (!placed) atomicExch(error_flag, 2);
+    ht_slot[idx] = slots[i];
+    if (freqs) ht_freq[idx] = freqs[i];
+    if (versions) ht_version[idx] = versions[i];
   }
 }
 
@@ -183,63 +211,56 @@ __global__ void k_insert_bulk(
 // fused hash dedup — replaces sort-based unique on the training hot path
 // ---------------------------------------------------------------------
 // The hash table itself deduplicates: pass A runs once per OCCURRENCE,
-// inserting the key if absent, counting frequency exactly, and claiming a
-// compact index [0, m) for the first toucher of this epoch (atomicExch on
-// a per-entry epoch stamp — exactly one winner). Pass B (per unique key)
-// applies admission + default-value init. Pass C (per occurrence) reads
-// back inverse indices and per-batch counts. Equivalent outputs to
-// torch.unique(return_inverse, return_counts) + the probe, without any
-// sort (the rocprim merge sorts were ~15% of the DLRM step).
+// inserting the key if absent and claiming a compact index [0, m) for the
+// first toucher of this epoch (atomicExch on a per-entry epoch stamp —
+// exactly one winner). Pass C (per occurrence) reads back inverse indices
+// and exact per-batch counts. Pass B (per unique key) applies the
+// frequency/version bookkeeping, admission + default-value init.
+// Equivalent outputs to torch.unique(return_inverse, return_counts) + the
+// probe, without any sort (the rocprim merge sorts were ~15% of the DLRM
+// step).
+//
+// Scalars that advance per step (epoch, step, unique count) come either by
+// value (eager path: the host knows them) or from a device scalar when its
+// pointer is non-null (hipGraph capture: k_bump_epoch advances them inside
+// the captured step, so replays keep deduplicating correctly with zero
+// host involvement).
 
 __global__ void k_dedup_pass_a(
     const int64_t* __restrict__ keys, int nnz, int64_t* __restrict__ ht_keys,
-    int32_t* __restrict__ ht_freq, int64_t* __restrict__ ht_version,
     int32_t* __restrict__ ht_epoch, int32_t* __restrict__ ht_compact,
-    int64_t cap_mask, int epoch, int64_t step,
+    int64_t cap_mask, const int32_t* __restrict__ epoch_dev, int epoch_val,
     int32_t* __restrict__ entry_counter, int32_t* __restrict__ m_counter,
     int64_t* __restrict__ uniq_keys, int64_t* __restrict__ compact_entry,
     int64_t* __restrict__ occ_entry, int32_t* __restrict__ error_flag) {
+  const int epoch = epoch_dev ? *epoch_dev : epoch_val;
   int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   for (; j < nnz; j += stride) {
     const int64_t key = keys[j];
-    uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-    for (int64_t probe = 0; probe <= cap_mask; ++probe) {
-      int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-      int64_t cur = ht_keys[idx];
-      if (cur != key) {
-        if (cur != EMPTY_KEY) continue;
-        int64_t prev = (int64_t)atomicCAS(
-            (unsigned long long*)&ht_keys[idx],
-            (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-        if (prev != EMPTY_KEY && prev != key) continue;
-        if (prev == EMPTY_KEY) atomicAdd(entry_counter, 1);
-      }
-      // freq/version updates moved to pass B (one per UNIQUE key via
-      // pass C's exact counts): hot keys were serializing thousands of
-      // per-occurrence atomics on one cache line here. The plain read
-      // short-circuits the epoch claim for already-claimed keys; racing
-      // first-touchers are resolved by the atomicExch.
-      if (ht_epoch[idx] != epoch) {
-        int old = atomicExch(&ht_epoch[idx], epoch);
-        if (old != epoch) {  // first toucher this step
-          int c = atomicAdd(m_counter, 1);
-          ht_compact[idx] = c;
-          uniq_keys[c] = key;
-          compact_entry[c] = idx;
-        }
-      }
-      occ_entry[j] = idx;  // pass C reads compact ids WITHOUT re-probing
-      goto next_j;
+    int64_t idx = ht_find_or_claim(ht_keys, cap_mask, key, entry_counter);
+    if (idx < 0) {
+      atomicExch(error_flag, 2);
+      continue;
     }
-    atomicExch(error_flag, 2);
-  next_j:;
+    // freq/version updates live in pass B (one per UNIQUE key via pass
+    // C's exact counts): hot keys were serializing thousands of
+    // per-occurrence atomics on one cache line here. The plain read
+    // short-circuits the epoch claim for already-claimed keys; racing
+    // first-touchers are resolved by the atomicExch.
+    if (ht_epoch[idx] != epoch) {
+      int old = atomicExch(&ht_epoch[idx], epoch);
+      if (old != epoch) {  // first toucher this step
+        int c = atomicAdd(m_counter, 1);
+        ht_compact[idx] = c;
+        uniq_keys[c] = key;
+        compact_entry[c] = idx;
+      }
+    }
+    occ_entry[j] = idx;  // pass C reads compact ids WITHOUT re-probing
   }
 }
 
-// Graph-capture pass A: epoch and step advance on-device (bumped by
-// k_bump_epoch inside the captured step) so replays keep deduplicating
-// correctly with zero host involvement.
 __global__ void k_bump_epoch(int32_t* __restrict__ epoch_dev,
                              int64_t* __restrict__ step_dev) {
   if (threadIdx.x == 0 && blockIdx.x == 0) {
@@ -248,153 +269,47 @@ __global__ void k_bump_epoch(int32_t* __restrict__ epoch_dev,
   }
 }
 
-__global__ void k_dedup_pass_a_dev(
-    const int64_t* __restrict__ keys, int nnz, int64_t* __restrict__ ht_keys,
-    int32_t* __restrict__ ht_freq, int64_t* __restrict__ ht_version,
-    int32_t* __restrict__ ht_epoch, int32_t* __restrict__ ht_compact,
-    int64_t cap_mask, const int32_t* __restrict__ epoch_dev,
-    const int64_t* __restrict__ step_dev,
-    int32_t* __restrict__ entry_counter, int32_t* __restrict__ m_counter,
-    int64_t* __restrict__ uniq_keys, int64_t* __restrict__ compact_entry,
-    int64_t* __restrict__ occ_entry, int32_t* __restrict__ error_flag) {
-  const int epoch = *epoch_dev;
-  const int64_t step = *step_dev;
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; j < nnz; j += stride) {
-    const int64_t key = keys[j];
-    uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-    for (int64_t probe = 0; probe <= cap_mask; ++probe) {
-      int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-      int64_t cur = ht_keys[idx];
-      if (cur != key) {
-        if (cur != EMPTY_KEY) continue;
-        int64_t prev = (int64_t)atomicCAS(
-            (unsigned long long*)&ht_keys[idx],
-            (unsigned long long)EMPTY_KEY, (unsigned long long)key);
-        if (prev != EMPTY_KEY && prev != key) continue;
-        if (prev == EMPTY_KEY) atomicAdd(entry_counter, 1);
-      }
-      // freq/version handled per-unique in pass B (see k_dedup_pass_a)
-      if (ht_epoch[idx] != epoch) {
-        int old = atomicExch(&ht_epoch[idx], epoch);
-        if (old != epoch) {
-          int c = atomicAdd(m_counter, 1);
-          ht_compact[idx] = c;
-          uniq_keys[c] = key;
-          compact_entry[c] = idx;
-        }
-      }
-      occ_entry[j] = idx;
-      goto next_j2;
-    }
-    atomicExch(error_flag, 2);
-  next_j2:;
-  }
-}
-
 // Pass B (per unique key): freq/version bookkeeping (one write per
 // unique key, using pass C's exact per-batch counts — runs AFTER pass
 // C), then admission + default-value init, slots out.
+// Padded mode (m_dev non-null; hipGraph capture and the sharded exchange):
+// the grid covers n = the nnz upper bound and the true unique count comes
+// from the device counter, so no host sync happens inside the captured
+// step. Tail entries get slot -1, and so does the wire-padding sentinel:
+// no admission, no metadata (PAD_KEY's composite-decomposed default row
+// would read far out of bounds of default_values).
 __global__ void k_dedup_pass_b(
     const int64_t* __restrict__ compact_entry,
-    const int64_t* __restrict__ uniq_keys, int m,
-    int32_t* __restrict__ ht_slot, int32_t* __restrict__ ht_freq,
-    int64_t* __restrict__ ht_version,
-    const int32_t* __restrict__ batch_counts, int64_t step,
+    const int64_t* __restrict__ uniq_keys, int n,
+    const int32_t* __restrict__ m_dev, int32_t* __restrict__ ht_slot,
+    int32_t* __restrict__ ht_freq, int64_t* __restrict__ ht_version,
+    const int32_t* __restrict__ batch_counts,
+    const int64_t* __restrict__ step_dev, int64_t step_val,
     int32_t* __restrict__ slot_counter, int max_slots,
     float* __restrict__ values, const float* __restrict__ default_values,
     int dim, int default_value_dim, int key_bits, int init_limit,
     int filter_freq, int32_t* __restrict__ out_slots,
     int32_t* __restrict__ error_flag) {
+  const int m = m_dev ? *m_dev : n;
+  const int64_t step = step_dev ? *step_dev : step_val;
   int64_t c = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t gstride = gridDim.x * (int64_t)blockDim.x;
-  for (; c < m; c += gstride) {
-  int64_t idx = compact_entry[c];
-  ht_freq[idx] += batch_counts[c];
-  ht_version[idx] = step;
-  int32_t slot = ht_slot[idx];
-  if (slot < 0 && ht_freq[idx] >= filter_freq) {
-    slot = atomicAdd(slot_counter, 1);
-    if (slot >= max_slots) {
-      atomicExch(error_flag, 1);
+  for (; c < n; c += gstride) {
+    if (m_dev && (c >= m || uniq_keys[c] == PAD_KEY)) {
       out_slots[c] = -1;
       continue;
     }
-    ht_slot[idx] = slot;
-    if (slot < init_limit) {
-      const int64_t key = uniq_keys[c];
-      int64_t dvrow;
-      if (key_bits > 0) {
-        int64_t mask = ((int64_t)1 << key_bits) - 1;
-        dvrow = (key >> key_bits) * default_value_dim +
-                (int64_t)((uint64_t)(key & mask) %
-                          (uint64_t)default_value_dim);
-      } else {
-        dvrow = (int64_t)((uint64_t)key % (uint64_t)default_value_dim);
-      }
-      const float* src = default_values + dvrow * dim;
-      float* dst = values + (int64_t)slot * dim;
-      for (int d = 0; d < dim; ++d) dst[d] = src[d];
-    }
+    int64_t idx = compact_entry[c];
+    int32_t freq = ht_freq[idx] + batch_counts[c];
+    ht_freq[idx] = freq;
+    ht_version[idx] = step;
+    int32_t slot = ht_slot[idx];
+    if (slot < 0 && freq >= filter_freq)
+      slot = ht_admit(uniq_keys[c], idx, ht_slot, slot_counter, max_slots,
+                      values, default_values, dim, default_value_dim,
+                      key_bits, init_limit, error_flag);
+    out_slots[c] = slot;
   }
-  out_slots[c] = slot;
-  }
-}
-
-// Padded pass B for hipGraph capture: grid covers n_cap (= nnz upper
-// bound); the true unique count comes from the device counter so no host
-// sync happens inside the captured step. Tail entries get slot -1.
-__global__ void k_dedup_pass_b_padded(
-    const int64_t* __restrict__ compact_entry,
-    const int64_t* __restrict__ uniq_keys, int n_cap,
-    const int32_t* __restrict__ m_dev, int32_t* __restrict__ ht_slot,
-    int32_t* __restrict__ ht_freq, int64_t* __restrict__ ht_version,
-    const int32_t* __restrict__ batch_counts,
-    const int64_t* __restrict__ step_dev,
-    int32_t* __restrict__ slot_counter,
-    int max_slots, float* __restrict__ values,
-    const float* __restrict__ default_values, int dim,
-    int default_value_dim, int key_bits, int init_limit, int filter_freq,
-    int32_t* __restrict__ out_slots, int32_t* __restrict__ error_flag) {
-  int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= n_cap) return;
-  if (c >= *m_dev || uniq_keys[c] == PAD_KEY) {
-    // tail slot, or the wire-padding sentinel of the sharded exchange:
-    // no admission, no metadata (PAD_KEY's composite-decomposed default
-    // row would read far out of bounds of default_values)
-    out_slots[c] = -1;
-    return;
-  }
-  int64_t idx = compact_entry[c];
-  ht_freq[idx] += batch_counts[c];
-  ht_version[idx] = *step_dev;
-  int32_t slot = ht_slot[idx];
-  if (slot < 0 && ht_freq[idx] >= filter_freq) {
-    slot = atomicAdd(slot_counter, 1);
-    if (slot >= max_slots) {
-      atomicExch(error_flag, 1);
-      out_slots[c] = -1;
-      return;
-    }
-    ht_slot[idx] = slot;
-    if (slot < init_limit) {
-      const int64_t key = uniq_keys[c];
-      int64_t dvrow;
-      if (key_bits > 0) {
-        int64_t mask = ((int64_t)1 << key_bits) - 1;
-        dvrow = (key >> key_bits) * default_value_dim +
-                (int64_t)((uint64_t)(key & mask) %
-                          (uint64_t)default_value_dim);
-      } else {
-        dvrow = (int64_t)((uint64_t)key % (uint64_t)default_value_dim);
-      }
-      const float* src = default_values + dvrow * dim;
-      float* dst = values + (int64_t)slot * dim;
-      for (int d = 0; d < dim; ++d) dst[d] = src[d];
-    }
-  }
-  out_slots[c] = slot;
 }
 
 // Zero-fill (float4-wide). Used instead of hipMemsetAsync because memset
@@ -504,36 +419,8 @@ __global__ void k_route_pad(
 // pad element maps to ONE unique (PAD_KEY), so generic index_add /
 // counting kernels serialize hundreds of thousands of atomics on a
 // single cache line (measured: torch index_add 783 us/step, pass C
-// 161 us). All kernels below skip pad elements outright.
-
-// Pass C variant that marks pads: inverse[j] = -1, no counts atomic.
-__global__ void k_dedup_pass_c_pad(
-    const int64_t* __restrict__ keys, int nnz,
-    const int64_t* __restrict__ ht_keys,
-    const int32_t* __restrict__ ht_compact, int64_t cap_mask,
-    int32_t* __restrict__ inverse, int32_t* __restrict__ counts,
-    int32_t* __restrict__ rank) {
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; j < nnz; j += stride) {
-    const int64_t key = keys[j];
-    if (key == PAD_KEY) {
-      inverse[j] = -1;
-      rank[j] = 0;
-      continue;
-    }
-    uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-    for (int64_t probe = 0; probe <= cap_mask; ++probe) {
-      int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-      if (ht_keys[idx] == key) {
-        int c = ht_compact[idx];
-        inverse[j] = c;
-        rank[j] = atomicAdd(&counts[c], 1);
-        break;
-      }
-    }
-  }
-}
+// 161 us). Pass C (given keys) and all kernels below skip pad elements
+// outright.
 
 // slots_elem[j] = inverse[j] < 0 ? -1 : slots[inverse[j]]
 // (replaces a .long() cast + index_select pair)
@@ -608,67 +495,30 @@ __global__ void k_rows_to_padded(const float* __restrict__ src,
   }
 }
 
-// Pass C (per occurrence): inverse + per-batch counts.
+// Pass C (per occurrence): inverse + exact per-batch counts. Index-direct:
+// pass A recorded each occurrence's hash entry, so inverse/rank need NO
+// re-probe of the table (the probe was ~half of the dedup cost at 213k
+// occurrences over a 16M-entry table). With `keys` given (owner side of
+// the sharded exchange) PAD_KEY elements get inverse -1 / rank 0 and
+// touch no counter.
 __global__ void k_dedup_pass_c(
-    const int64_t* __restrict__ keys, int nnz,
-    const int64_t* __restrict__ ht_keys,
-    const int32_t* __restrict__ ht_compact, int64_t cap_mask,
+    const int64_t* __restrict__ keys, const int64_t* __restrict__ occ_entry,
+    int nnz, const int32_t* __restrict__ ht_compact,
     int32_t* __restrict__ inverse, int32_t* __restrict__ counts,
     int32_t* __restrict__ rank) {
   int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   for (; j < nnz; j += stride) {
-    const int64_t key = keys[j];
-    uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-    for (int64_t probe = 0; probe <= cap_mask; ++probe) {
-      int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-      if (ht_keys[idx] == key) {
-        int c = ht_compact[idx];
-        inverse[j] = c;
-        // the counter value doubles as this occurrence's rank within its
-        // key, letting the CSR order build become a direct scatter
-        // (k_csr_scatter) instead of a second atomic-cursor pass
-        rank[j] = atomicAdd(&counts[c], 1);
-        break;
-      }
-    }
-  }
-}
-
-// Index-direct pass C: pass A recorded each occurrence's hash entry, so
-// inverse/rank need NO re-probe of the table (the probe was ~half of
-// the dedup cost at 213k occurrences over a 16M-entry table).
-__global__ void k_dedup_pass_c_idx(
-    const int64_t* __restrict__ occ_entry, int nnz,
-    const int32_t* __restrict__ ht_compact,
-    int32_t* __restrict__ inverse, int32_t* __restrict__ counts,
-    int32_t* __restrict__ rank) {
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; j < nnz; j += stride) {
-    int c = ht_compact[occ_entry[j]];
-    inverse[j] = c;
-    rank[j] = atomicAdd(&counts[c], 1);
-  }
-}
-
-// PAD-aware variant for the owner side of the sharded exchange.
-__global__ void k_dedup_pass_c_idx_pad(
-    const int64_t* __restrict__ keys,
-    const int64_t* __restrict__ occ_entry, int nnz,
-    const int32_t* __restrict__ ht_compact,
-    int32_t* __restrict__ inverse, int32_t* __restrict__ counts,
-    int32_t* __restrict__ rank) {
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; j < nnz; j += stride) {
-    if (keys[j] == PAD_KEY) {
+    if (keys && keys[j] == PAD_KEY) {
       inverse[j] = -1;
       rank[j] = 0;
       continue;
     }
     int c = ht_compact[occ_entry[j]];
     inverse[j] = c;
+    // the counter value doubles as this occurrence's rank within its
+    // key, letting the CSR order build become a direct scatter
+    // (k_csr_scatter) instead of a second atomic-cursor pass
     rank[j] = atomicAdd(&counts[c], 1);
   }
 }
@@ -746,24 +596,9 @@ __global__ void k_lookup(
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t gstride = gridDim.x * (int64_t)blockDim.x;
   for (; i < n; i += gstride) {
-    const int64_t key = keys[i];
-    uint64_t h = mix_hash((uint64_t)key) & (uint64_t)cap_mask;
-    bool found = false;
-    for (int64_t probe = 0; probe <= cap_mask; ++probe) {
-      int64_t idx = (int64_t)((h + probe) & (uint64_t)cap_mask);
-      int64_t cur = ht_keys[idx];
-      if (cur == key) {
-        out_slots[i] = ht_slot[idx];
-        if (out_entry) out_entry[i] = idx;
-        found = true;
-        break;
-      }
-      if (cur == EMPTY_KEY) break;
-    }
-    if (!found) {
-      out_slots[i] = -1;
-      if (out_entry) out_entry[i] = -1;
-    }
+    int64_t idx = ht_find(ht_keys, cap_mask, keys[i]);
+    out_slots[i] = idx >= 0 ? ht_slot[idx] : -1;
+    if (out_entry) out_entry[i] = idx;
   }
 }
 
@@ -1225,6 +1060,13 @@ static inline int n_blocks(int64_t total, int block = kBlock) {
   return (int)std::min<int64_t>(b, 65535);
 }
 
+// Zero n 4-byte words (fp32 or int32) on the stream; see k_zero_f32 for
+// why this is not hipMemsetAsync.
+static inline void zero_fill(void* p, int64_t n, hipStream_t stream) {
+  k_zero_f32<<<n_blocks((n + 3) / 4), kBlock, 0, stream>>>(
+      static_cast<float*>(p), n);
+}
+
 torch::Tensor ht_lookup_insert(
     torch::Tensor keys, torch::Tensor counts, torch::Tensor ht_keys,
     torch::Tensor ht_slot, torch::Tensor ht_freq, torch::Tensor ht_version,
@@ -1254,21 +1096,28 @@ torch::Tensor ht_lookup_insert(
   return out;
 }
 
+// The dedup passes take each per-step scalar (epoch, step, unique count)
+// either from a device scalar (hipGraph capture) or by value when the
+// optional tensor is None (eager: the host knows it).
+template <typename T>
+static inline const T* opt_ptr(const c10::optional<torch::Tensor>& t) {
+  return t.has_value() ? t->data_ptr<T>() : nullptr;
+}
+
 torch::Tensor ht_dedup_a(torch::Tensor keys, torch::Tensor ht_keys,
-                         torch::Tensor ht_freq, torch::Tensor ht_version,
                          torch::Tensor ht_epoch, torch::Tensor ht_compact,
-                         int64_t epoch, int64_t step,
-                         torch::Tensor entry_counter, torch::Tensor m_counter,
-                         torch::Tensor uniq_keys, torch::Tensor compact_entry,
+                         c10::optional<torch::Tensor> epoch_dev,
+                         int64_t epoch, torch::Tensor entry_counter,
+                         torch::Tensor m_counter, torch::Tensor uniq_keys,
+                         torch::Tensor compact_entry,
                          torch::Tensor occ_entry, torch::Tensor error_flag) {
   int64_t nnz = keys.numel();
   if (nnz == 0) return m_counter;
   auto stream = current_stream();
   k_dedup_pass_a<<<n_blocks(nnz), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
-      ht_freq.data_ptr<int32_t>(), ht_version.data_ptr<int64_t>(),
       ht_epoch.data_ptr<int32_t>(), ht_compact.data_ptr<int32_t>(),
-      ht_keys.numel() - 1, (int)epoch, step,
+      ht_keys.numel() - 1, opt_ptr<int32_t>(epoch_dev), (int)epoch,
       entry_counter.data_ptr<int32_t>(), m_counter.data_ptr<int32_t>(),
       uniq_keys.data_ptr<int64_t>(), compact_entry.data_ptr<int64_t>(),
       occ_entry.data_ptr<int64_t>(), error_flag.data_ptr<int32_t>());
@@ -1276,23 +1125,26 @@ torch::Tensor ht_dedup_a(torch::Tensor keys, torch::Tensor ht_keys,
 }
 
 torch::Tensor ht_dedup_b(torch::Tensor compact_entry, torch::Tensor uniq_keys,
+                         c10::optional<torch::Tensor> m_dev,
                          torch::Tensor ht_slot, torch::Tensor ht_freq,
                          torch::Tensor ht_version,
-                         torch::Tensor batch_counts, int64_t step,
+                         torch::Tensor batch_counts,
+                         c10::optional<torch::Tensor> step_dev, int64_t step,
                          torch::Tensor slot_counter, int64_t max_slots,
                          torch::Tensor values, torch::Tensor default_values,
                          int64_t dvd_per_table, int64_t key_bits,
                          int64_t init_limit, int64_t filter_freq,
                          torch::Tensor error_flag) {
-  int m = uniq_keys.numel();
-  auto slots = torch::empty({m}, ht_slot.options());
-  if (m == 0) return slots;
+  int n = uniq_keys.numel();
+  auto slots = torch::empty({n}, ht_slot.options());
+  if (n == 0) return slots;
   auto stream = current_stream();
-  k_dedup_pass_b<<<n_blocks(m), kBlock, 0, stream>>>(
-      compact_entry.data_ptr<int64_t>(), uniq_keys.data_ptr<int64_t>(), m,
-      ht_slot.data_ptr<int32_t>(), ht_freq.data_ptr<int32_t>(),
-      ht_version.data_ptr<int64_t>(), batch_counts.data_ptr<int32_t>(),
-      step, slot_counter.data_ptr<int32_t>(), (int)max_slots,
+  k_dedup_pass_b<<<n_blocks(n), kBlock, 0, stream>>>(
+      compact_entry.data_ptr<int64_t>(), uniq_keys.data_ptr<int64_t>(), n,
+      opt_ptr<int32_t>(m_dev), ht_slot.data_ptr<int32_t>(),
+      ht_freq.data_ptr<int32_t>(), ht_version.data_ptr<int64_t>(),
+      batch_counts.data_ptr<int32_t>(), opt_ptr<int64_t>(step_dev), step,
+      slot_counter.data_ptr<int32_t>(), (int)max_slots,
       values.data_ptr<float>(), default_values.data_ptr<float>(),
       values.size(1), (int)dvd_per_table, (int)key_bits, (int)init_limit,
       (int)filter_freq, slots.data_ptr<int32_t>(),
@@ -1334,25 +1186,6 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> route_pad(
   return {send_keys, send_cnt, route_pos};
 }
 
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ht_dedup_c_pad(
-    torch::Tensor keys, torch::Tensor ht_keys, torch::Tensor ht_compact,
-    int64_t m) {
-  int64_t nnz = keys.numel();
-  auto inverse = torch::empty({nnz}, ht_compact.options());
-  auto rank = torch::empty({nnz}, ht_compact.options());
-  auto counts = torch::empty({m}, ht_compact.options());
-  if (nnz == 0) return {inverse, counts, rank};
-  auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m + 3) / 4), kBlock, 0, stream>>>(
-      reinterpret_cast<float*>(counts.data_ptr<int32_t>()), m);
-  k_dedup_pass_c_pad<<<n_blocks(nnz), kBlock, 0, stream>>>(
-      keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
-      ht_compact.data_ptr<int32_t>(), ht_keys.numel() - 1,
-      inverse.data_ptr<int32_t>(), counts.data_ptr<int32_t>(),
-      rank.data_ptr<int32_t>());
-  return {inverse, counts, rank};
-}
-
 torch::Tensor slots_gather_pad(torch::Tensor inverse, torch::Tensor slots) {
   int64_t nnz = inverse.numel();
   auto out = torch::empty({nnz}, slots.options());
@@ -1368,8 +1201,7 @@ torch::Tensor cnt_sum_pad(torch::Tensor inverse, torch::Tensor cnt,
   int64_t nnz = inverse.numel();
   auto out = torch::empty({m_cap}, cnt.options());
   auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m_cap + 3) / 4), kBlock, 0, stream>>>(
-      reinterpret_cast<float*>(out.data_ptr<int32_t>()), m_cap);
+  zero_fill(out.data_ptr<int32_t>(), m_cap, stream);
   if (nnz)
     k_cnt_sum_pad<<<n_blocks(nnz), kBlock, 0, stream>>>(
         inverse.data_ptr<int32_t>(), cnt.data_ptr<int32_t>(), (int)nnz,
@@ -1383,8 +1215,7 @@ torch::Tensor rows_segsum_pad(torch::Tensor grad, torch::Tensor inverse,
   int dim = grad.size(1);
   auto out = torch::empty({m_cap, (int64_t)dim}, grad.options());
   auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m_cap * dim + 3) / 4), kBlock, 0, stream>>>(
-      out.data_ptr<float>(), m_cap * dim);
+  zero_fill(out.data_ptr<float>(), m_cap * dim, stream);
   if (nnz)
     k_rows_segsum_pad<<<n_blocks(nnz * dim), kBlock, 0, stream>>>(
         grad.data_ptr<float>(), inverse.data_ptr<int32_t>(), (int)nnz, dim,
@@ -1434,111 +1265,26 @@ torch::Tensor rows_to_padded(torch::Tensor src, torch::Tensor route_pos,
   int dim = src.size(1);
   auto dst = torch::empty({out_rows, (int64_t)dim}, src.options());
   auto stream = current_stream();
-  k_zero_f32<<<n_blocks((out_rows * dim + 3) / 4), kBlock, 0, stream>>>(
-      dst.data_ptr<float>(), out_rows * dim);
+  zero_fill(dst.data_ptr<float>(), out_rows * dim, stream);
   k_rows_to_padded<<<n_blocks((int64_t)n_cap * dim), kBlock, 0, stream>>>(
       src.data_ptr<float>(), route_pos.data_ptr<int32_t>(),
       m_dev.data_ptr<int32_t>(), n_cap, dim, dst.data_ptr<float>());
   return dst;
 }
 
-torch::Tensor ht_dedup_a_dev(
-    torch::Tensor keys, torch::Tensor ht_keys, torch::Tensor ht_freq,
-    torch::Tensor ht_version, torch::Tensor ht_epoch,
-    torch::Tensor ht_compact, torch::Tensor epoch_dev,
-    torch::Tensor step_dev, torch::Tensor entry_counter,
-    torch::Tensor m_counter, torch::Tensor uniq_keys,
-    torch::Tensor compact_entry, torch::Tensor occ_entry,
-    torch::Tensor error_flag) {
-  int64_t nnz = keys.numel();
-  if (nnz == 0) return m_counter;
-  auto stream = current_stream();
-  k_dedup_pass_a_dev<<<n_blocks(nnz), kBlock, 0, stream>>>(
-      keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
-      ht_freq.data_ptr<int32_t>(), ht_version.data_ptr<int64_t>(),
-      ht_epoch.data_ptr<int32_t>(), ht_compact.data_ptr<int32_t>(),
-      ht_keys.numel() - 1, epoch_dev.data_ptr<int32_t>(),
-      step_dev.data_ptr<int64_t>(), entry_counter.data_ptr<int32_t>(),
-      m_counter.data_ptr<int32_t>(), uniq_keys.data_ptr<int64_t>(),
-      compact_entry.data_ptr<int64_t>(), occ_entry.data_ptr<int64_t>(),
-      error_flag.data_ptr<int32_t>());
-  return m_counter;
-}
-
-torch::Tensor ht_dedup_b_padded(
-    torch::Tensor compact_entry, torch::Tensor uniq_keys,
-    torch::Tensor m_dev, torch::Tensor ht_slot, torch::Tensor ht_freq,
-    torch::Tensor ht_version, torch::Tensor batch_counts,
-    torch::Tensor step_dev,
-    torch::Tensor slot_counter, int64_t max_slots, torch::Tensor values,
-    torch::Tensor default_values, int64_t dvd_per_table, int64_t key_bits,
-    int64_t init_limit, int64_t filter_freq, torch::Tensor error_flag) {
-  int n_cap = uniq_keys.numel();
-  auto slots = torch::empty({n_cap}, ht_slot.options());
-  if (n_cap == 0) return slots;
-  auto stream = current_stream();
-  k_dedup_pass_b_padded<<<n_blocks(n_cap), kBlock, 0, stream>>>(
-      compact_entry.data_ptr<int64_t>(), uniq_keys.data_ptr<int64_t>(),
-      n_cap, m_dev.data_ptr<int32_t>(), ht_slot.data_ptr<int32_t>(),
-      ht_freq.data_ptr<int32_t>(), ht_version.data_ptr<int64_t>(),
-      batch_counts.data_ptr<int32_t>(), step_dev.data_ptr<int64_t>(),
-      slot_counter.data_ptr<int32_t>(),
-      (int)max_slots, values.data_ptr<float>(),
-      default_values.data_ptr<float>(), values.size(1), (int)dvd_per_table,
-      (int)key_bits, (int)init_limit, (int)filter_freq,
-      slots.data_ptr<int32_t>(), error_flag.data_ptr<int32_t>());
-  return slots;
-}
-
+// keys: None, or the received keys whose PAD_KEY elements pass C skips.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ht_dedup_c(
-    torch::Tensor keys, torch::Tensor ht_keys, torch::Tensor ht_compact,
-    int64_t m) {
-  int64_t nnz = keys.numel();
+    c10::optional<torch::Tensor> keys, torch::Tensor occ_entry,
+    torch::Tensor ht_compact, int64_t m) {
+  int64_t nnz = occ_entry.numel();
   auto inverse = torch::empty({nnz}, ht_compact.options());
   auto rank = torch::empty({nnz}, ht_compact.options());
   auto counts = torch::empty({m}, ht_compact.options());
   if (nnz == 0) return {inverse, counts, rank};
   auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m + 3) / 4), kBlock, 0, stream>>>(
-      reinterpret_cast<float*>(counts.data_ptr<int32_t>()), m);
+  zero_fill(counts.data_ptr<int32_t>(), m, stream);
   k_dedup_pass_c<<<n_blocks(nnz), kBlock, 0, stream>>>(
-      keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
-      ht_compact.data_ptr<int32_t>(), ht_keys.numel() - 1,
-      inverse.data_ptr<int32_t>(), counts.data_ptr<int32_t>(),
-      rank.data_ptr<int32_t>());
-  return {inverse, counts, rank};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ht_dedup_c_idx(
-    torch::Tensor occ_entry, torch::Tensor ht_compact, int64_t m) {
-  int64_t nnz = occ_entry.numel();
-  auto inverse = torch::empty({nnz}, ht_compact.options());
-  auto rank = torch::empty({nnz}, ht_compact.options());
-  auto counts = torch::empty({m}, ht_compact.options());
-  if (nnz == 0) return {inverse, counts, rank};
-  auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m + 3) / 4), kBlock, 0, stream>>>(
-      reinterpret_cast<float*>(counts.data_ptr<int32_t>()), m);
-  k_dedup_pass_c_idx<<<n_blocks(nnz), kBlock, 0, stream>>>(
-      occ_entry.data_ptr<int64_t>(), (int)nnz,
-      ht_compact.data_ptr<int32_t>(), inverse.data_ptr<int32_t>(),
-      counts.data_ptr<int32_t>(), rank.data_ptr<int32_t>());
-  return {inverse, counts, rank};
-}
-
-std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ht_dedup_c_idx_pad(
-    torch::Tensor keys, torch::Tensor occ_entry, torch::Tensor ht_compact,
-    int64_t m) {
-  int64_t nnz = occ_entry.numel();
-  auto inverse = torch::empty({nnz}, ht_compact.options());
-  auto rank = torch::empty({nnz}, ht_compact.options());
-  auto counts = torch::empty({m}, ht_compact.options());
-  if (nnz == 0) return {inverse, counts, rank};
-  auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m + 3) / 4), kBlock, 0, stream>>>(
-      reinterpret_cast<float*>(counts.data_ptr<int32_t>()), m);
-  k_dedup_pass_c_idx_pad<<<n_blocks(nnz), kBlock, 0, stream>>>(
-      keys.data_ptr<int64_t>(), occ_entry.data_ptr<int64_t>(), (int)nnz,
+      opt_ptr<int64_t>(keys), occ_entry.data_ptr<int64_t>(), (int)nnz,
       ht_compact.data_ptr<int32_t>(), inverse.data_ptr<int32_t>(),
       counts.data_ptr<int32_t>(), rank.data_ptr<int32_t>());
   return {inverse, counts, rank};
@@ -1828,8 +1574,7 @@ torch::Tensor group_pooled_bwd_strided(
       {m, dim}, grad_out.options().dtype(torch::kFloat32));
   if (m * dim == 0) return grad_unique;
   auto stream = current_stream();
-  k_zero_f32<<<n_blocks((m * dim + 3) / 4), kBlock, 0, stream>>>(
-      grad_unique.data_ptr<float>(), m * dim);
+  zero_fill(grad_unique.data_ptr<float>(), m * dim, stream);
   const float* wptr =
       weights.defined() && weights.numel() ? weights.data_ptr<float>()
                                            : nullptr;
@@ -2003,13 +1748,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_b", &ht_dedup_b);
-  mod.def("ht_dedup_b_padded", &ht_dedup_b_padded);
-  mod.def("ht_dedup_a_dev", &ht_dedup_a_dev);
   mod.def("bump_epoch", &bump_epoch);
   mod.def("bump_epoch_only", &bump_epoch_only);
   mod.def("route_pad", &route_pad);
   mod.def("rows_to_padded", &rows_to_padded);
-  mod.def("ht_dedup_c_pad", &ht_dedup_c_pad);
   mod.def("slots_gather_pad", &slots_gather_pad);
   mod.def("cnt_sum_pad", &cnt_sum_pad);
   mod.def("rows_segsum_pad", &rows_segsum_pad);
@@ -2017,8 +1759,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("gather_host_rows", &gather_host_rows);
   mod.def("scatter_host_rows", &scatter_host_rows);
   mod.def("ht_dedup_c", &ht_dedup_c);
-  mod.def("ht_dedup_c_idx", &ht_dedup_c_idx);
-  mod.def("ht_dedup_c_idx_pad", &ht_dedup_c_idx_pad);
   mod.def("csr_order", &csr_order);
   mod.def("csr_scatter", &csr_scatter);
   mod.def("ht_insert_bulk", &ht_insert_bulk);

@@ -246,36 +246,59 @@ class HbmStorage:
         self._step_dev = torch.tensor([get_global_step()],
                                       dtype=torch.int64, device=self.device)
 
-    def dedup_lookup_capture(self, values_cat: torch.Tensor):
-        """Sync-free, fixed-shape dedup+probe for hipGraph capture: all
-        outputs are nnz-padded; the true unique count lives in a device
-        counter consumed by the padded pass B (tail slots = -1)."""
-        nnz = values_cat.numel()
-        self.ext.bump_epoch(self._epoch_dev, self._step_dev)
+    # ---------------- fused hash dedup: the three passes ----------------
+    def _dedup_claim(self, keys: torch.Tensor, epoch_dev=None):
+        """Pass A: allocate the step's buffers, then find-or-insert every
+        occurrence and claim a compact index per unique key. The epoch is
+        the device scalar when given (capture), else the host counter.
+        Returns (uniq_buf, centry_buf, occ_entry, m_counter); the first
+        three are nnz-padded, m_counter is the device unique count."""
+        nnz = keys.numel()
         uniq_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
         centry_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
         occ_entry = torch.empty(nnz, dtype=torch.int64, device=self.device)
         m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self._last_m_dev = m_counter
-        self.ext.ht_dedup_a_dev(values_cat, self.ht_keys, self.ht_freq,
-                                self.ht_version, self.ht_epoch,
-                                self.ht_compact, self._epoch_dev,
-                                self._step_dev, self.entry_counter,
-                                m_counter, uniq_buf, centry_buf,
-                                occ_entry, self.error_flag)
-        # pass C first: its exact per-batch counts feed pass B's single
-        # per-unique freq update (pass A is claim-only — hot keys no
-        # longer serialize per-occurrence atomics; index-direct: no
-        # table re-probe)
-        inverse, counts, rank = self.ext.ht_dedup_c_idx(
-            occ_entry, self.ht_compact, nnz)
-        self._last_rank = rank  # consumed by collection._prep_backward
-        slots = self.ext.ht_dedup_b_padded(
-            centry_buf, uniq_buf, m_counter, self.ht_slot, self.ht_freq,
-            self.ht_version, counts, self._step_dev,
+        self.ext.ht_dedup_a(keys, self.ht_keys, self.ht_epoch,
+                            self.ht_compact, epoch_dev, self._epoch,
+                            self.entry_counter, m_counter, uniq_buf,
+                            centry_buf, occ_entry, self.error_flag)
+        return uniq_buf, centry_buf, occ_entry, m_counter
+
+    def _dedup_count(self, occ_entry: torch.Tensor, m: int, pad_keys=None):
+        """Pass C: (inverse, counts [m], rank) from the entries pass A
+        recorded (index-direct: no table re-probe). With pad_keys, PAD_KEY
+        elements get inverse -1 and touch no counter."""
+        return self.ext.ht_dedup_c(pad_keys, occ_entry, self.ht_compact, m)
+
+    def _dedup_admit(self, centry, uniq, counts, step=0, m_dev=None):
+        """Pass B: one freq/version update per unique key from pass C's
+        counts, then admission; returns slots. With m_dev (capture) the
+        inputs are nnz-padded, the step comes from the device scalar, and
+        the tail and PAD_KEY get slot -1."""
+        return self.ext.ht_dedup_b(
+            centry, uniq, m_dev, self.ht_slot, self.ht_freq,
+            self.ht_version, counts,
+            self._step_dev if m_dev is not None else None, step,
             self.slot_counter, self.max_slots, self.values,
             self.default_values, self.dvd_per_table, self.key_bits,
             self._init_limit(), self.filter_freq, self.error_flag)
+
+    def dedup_lookup_capture(self, values_cat: torch.Tensor):
+        """Sync-free, fixed-shape dedup+probe for hipGraph capture: all
+        outputs are nnz-padded; the true unique count lives in a device
+        counter consumed by the padded pass B (tail slots = -1)."""
+        self.ext.bump_epoch(self._epoch_dev, self._step_dev)
+        uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
+            values_cat, self._epoch_dev)
+        self._last_m_dev = m_counter
+        # pass C first: its exact per-batch counts feed pass B's single
+        # per-unique freq update (pass A is claim-only — hot keys no
+        # longer serialize per-occurrence atomics)
+        inverse, counts, rank = self._dedup_count(occ_entry,
+                                                  values_cat.numel())
+        self._last_rank = rank  # consumed by collection._prep_backward
+        slots = self._dedup_admit(centry_buf, uniq_buf, counts,
+                                  m_dev=m_counter)
         return uniq_buf, inverse, counts, slots
 
     def dedup_only_capture(self, values_cat: torch.Tensor):
@@ -288,21 +311,12 @@ class HbmStorage:
         Returns (uniq_buf [nnz] padded, inverse i32 [nnz], counts i32
         [nnz] padded, m_counter device scalar). Capture-safe: no host
         syncs, all shapes static."""
-        nnz = values_cat.numel()
         self.ext.bump_epoch(self._epoch_dev, self._step_dev)
-        uniq_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        centry_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        occ_entry = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        uniq_buf, _centry, occ_entry, m_counter = self._dedup_claim(
+            values_cat, self._epoch_dev)
         self._last_m_dev = m_counter
-        self.ext.ht_dedup_a_dev(values_cat, self.ht_keys, self.ht_freq,
-                                self.ht_version, self.ht_epoch,
-                                self.ht_compact, self._epoch_dev,
-                                self._step_dev, self.entry_counter,
-                                m_counter, uniq_buf, centry_buf,
-                                occ_entry, self.error_flag)
-        inverse, counts, rank = self.ext.ht_dedup_c_idx(
-            occ_entry, self.ht_compact, nnz)
+        inverse, counts, rank = self._dedup_count(occ_entry,
+                                                  values_cat.numel())
         self._last_rank = rank
         return uniq_buf, inverse, counts, m_counter
 
@@ -317,28 +331,16 @@ class HbmStorage:
         the step already advanced in the requester pass)."""
         nnz = recv_keys.numel()
         self.ext.bump_epoch_only(self._epoch_dev)
-        uniq_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        centry_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        occ_entry = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.ext.ht_dedup_a_dev(recv_keys, self.ht_keys, self.ht_freq,
-                                self.ht_version, self.ht_epoch,
-                                self.ht_compact, self._epoch_dev,
-                                self._step_dev, self.entry_counter,
-                                m_counter, uniq_buf, centry_buf,
-                                occ_entry, self.error_flag)
-        # PAD-aware, index-direct pass C: pad elements get inverse -1
-        # and never touch the shared counters (a naive path serialized
-        # ~10^5 atomics on PAD_KEY's single cache line)
-        inverse, _counts_c, _rank = self.ext.ht_dedup_c_idx_pad(
-            recv_keys, occ_entry, self.ht_compact, nnz)
+        uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
+            recv_keys, self._epoch_dev)
+        # PAD-aware pass C: pad elements get inverse -1 and never touch
+        # the shared counters (a naive path serialized ~10^5 atomics on
+        # PAD_KEY's single cache line)
+        inverse, _counts_c, _rank = self._dedup_count(occ_entry, nnz,
+                                                      pad_keys=recv_keys)
         cnt_sum = self.ext.cnt_sum_pad(inverse, recv_cnt, nnz)
-        slots = self.ext.ht_dedup_b_padded(
-            centry_buf, uniq_buf, m_counter, self.ht_slot, self.ht_freq,
-            self.ht_version, cnt_sum, self._step_dev,
-            self.slot_counter, self.max_slots, self.values,
-            self.default_values, self.dvd_per_table, self.key_bits,
-            self._init_limit(), self.filter_freq, self.error_flag)
+        slots = self._dedup_admit(centry_buf, uniq_buf, cnt_sum,
+                                  m_dev=m_counter)
         return uniq_buf, inverse, slots
 
     def prefers_dedup(self) -> bool:
@@ -362,15 +364,8 @@ class HbmStorage:
         nnz = values_cat.numel()
         self._ensure_capacity(nnz)
         self._epoch += 1
-        uniq_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        centry_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        occ_entry = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.ext.ht_dedup_a(values_cat, self.ht_keys, self.ht_freq,
-                            self.ht_version, self.ht_epoch, self.ht_compact,
-                            self._epoch, step, self.entry_counter, m_counter,
-                            uniq_buf, centry_buf, occ_entry,
-                            self.error_flag)
+        uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
+            values_cat)
         # one D2H sync (as torch.unique pays); piggyback the real counters
         # so capacity hints don't inflate by nnz per step (which caused
         # needless rehashes on high-uniqueness workloads)
@@ -382,16 +377,9 @@ class HbmStorage:
         self.observe_uniq_ratio(m, nnz)
         uniq = uniq_buf[:m]
         # pass C first: exact counts feed pass B's per-unique freq update
-        # (index-direct: pass A recorded each occurrence's entry)
-        inverse, counts, rank = self.ext.ht_dedup_c_idx(
-            occ_entry, self.ht_compact, m)
+        inverse, counts, rank = self._dedup_count(occ_entry, m)
         self._last_rank = rank  # consumed by collection._prep_backward
-        slots = self.ext.ht_dedup_b(
-            centry_buf[:m], uniq, self.ht_slot, self.ht_freq,
-            self.ht_version, counts, step,
-            self.slot_counter, self.max_slots, self.values,
-            self.default_values, self.dvd_per_table, self.key_bits,
-            self._init_limit(), self.filter_freq, self.error_flag)
+        slots = self._dedup_admit(centry_buf[:m], uniq, counts, step=step)
         return uniq, inverse, counts, slots
 
     def _use_no_permission(self) -> bool:

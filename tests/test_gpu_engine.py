@@ -257,3 +257,129 @@ def test_bulk_insert_lookup_beyond_grid_cap():
     assert bool((got >= 0).all()), "tail keys lost by bulk insert"
     torch.testing.assert_close(got.long(), probe - (n - 1_000_000)
                                + (n - 1_000_000))
+
+
+def _dedup_storage(composite):
+    """Fresh HbmStorage with filter_freq = 2; the composite flavour holds
+    two tables' default rows behind 48-bit composite keys."""
+    from deeprec_amd.ops.hip_backend import HbmStorage
+
+    opt = EmbeddingVariableOption(
+        init_capacity=2048,
+        filter_option=CounterFilter(filter_freq=2),
+        init_option=InitializerOption(default_value_dim=32))
+    st = HbmStorage(8, opt, device=DEV,
+                    generator=torch.Generator().manual_seed(5))
+    if composite:
+        st.key_bits, st.dvd_per_table = 48, 16
+    return st
+
+
+def _default_rows(st, keys):
+    """Row of st.default_values that initializes each key (CPU int64)."""
+    if st.key_bits > 0:
+        mask = (1 << st.key_bits) - 1
+        return ((keys >> st.key_bits) * st.dvd_per_table
+                + (keys & mask) % st.dvd_per_table)
+    return keys % st.default_value_dim
+
+
+def _check_dedup_step(st, keys, out, m, freq_after, padded):
+    """One dedup step's outputs against torch.unique, as key -> value maps
+    (the order of uniques is decided by atomics)."""
+    uniq, inverse, counts, slots = (t.cpu() for t in out)
+    keys = keys.cpu()
+    ref_u, ref_c = torch.unique(keys, return_counts=True)
+    assert m == ref_u.numel()
+    order = torch.argsort(uniq[:m])
+    assert torch.equal(uniq[:m][order], ref_u)
+    assert torch.equal(uniq[inverse.long()], keys)
+    assert torch.equal(counts[:m][order].long(), ref_c)
+    if padded:
+        assert slots.numel() == keys.numel()
+        assert bool((slots[m:] == -1).all())
+    else:
+        assert slots.numel() == m
+    s = slots[:m][order]
+    want = torch.tensor([freq_after[int(k)] >= 2 for k in ref_u])
+    assert torch.equal(s >= 0, want)
+    adm = s[want].long()
+    assert adm.unique().numel() == adm.numel()  # distinct slots
+    # nothing trains here, so every admitted row still is its default row
+    rows = _default_rows(st, ref_u[want])
+    assert torch.equal(st.values.cpu()[adm], st.default_values.cpu()[rows])
+
+
+def _entry_map(st):
+    keys, _slots, freqs, versions = st._export_entries()
+    return {int(k): (int(f), int(v)) for k, f, v in
+            zip(keys.cpu(), freqs.cpu(), versions.cpu())}
+
+
+@pytest.mark.parametrize("composite", [False, True])
+def test_dedup_entry_points_agree(composite):
+    """The eager dedup_lookup and the capture-mode dedup_lookup_capture
+    (plain kernel launches once enable_graph_mode has run) see the same
+    keys for three steps and must agree with torch.unique, with the
+    admission rule and with each other's table contents; the owner-side
+    entry point is checked on a PAD_KEY-padded exchange."""
+    pad_key = 2 ** 63 - 1
+    gen = torch.Generator().manual_seed(17 + composite)
+    ids = torch.randint(0, 1 << 40, (300,), generator=gen)
+    if composite:
+        ids = ids + (torch.randint(0, 2, (300,), generator=gen) << 48)
+    st_a, st_b = _dedup_storage(composite), _dedup_storage(composite)
+    GLOBAL_STEP.value = 10
+    st_b.enable_graph_mode(1000, 1024)
+    freq, version = {}, {}
+    for i in range(3):
+        step = 10 + 1 + i  # the value B's device step counter takes
+        keys = torch.cat([ids[torch.randint(0, 300, (657,), generator=gen)],
+                          ids[i].repeat(120)])  # 777 keys, one hot
+        keys = keys[torch.randperm(777, generator=gen)].to(DEV)
+        for k in keys.tolist():
+            freq[k] = freq.get(k, 0) + 1
+            version[k] = step
+        out_a = st_a.dedup_lookup(keys, step)
+        _check_dedup_step(st_a, keys, out_a, out_a[0].numel(), freq, False)
+        out_b = st_b.dedup_lookup_capture(keys)
+        _check_dedup_step(st_b, keys, out_b, int(st_b._last_m_dev), freq,
+                          True)
+    ref = {k: (freq[k], version[k]) for k in freq}
+    assert _entry_map(st_a) == ref
+    assert _entry_map(st_b) == ref
+
+    # owner side: each real key up to three times, about one third pads
+    st_c = _dedup_storage(composite)
+    st_c.enable_graph_mode(1000, 1024)
+    real = ids[:200].repeat_interleave(
+        torch.randint(1, 4, (200,), generator=gen))
+    n_pad = real.numel() // 2
+    recv = torch.cat([real, torch.full((n_pad,), pad_key)])
+    recv = recv[torch.randperm(recv.numel(), generator=gen)]
+    is_pad = recv == pad_key
+    total = {}
+    for _ in range(2):
+        cnt = torch.randint(1, 3, (recv.numel(),), generator=gen,
+                            dtype=torch.int32)
+        cnt[is_pad] = 0
+        for k, c in zip(recv[~is_pad].tolist(), cnt[~is_pad].tolist()):
+            total[k] = total.get(k, 0) + c
+        uniq, inverse, slots = (t.cpu() for t in
+                                st_c.dedup_lookup_capture_owner(
+                                    recv.to(DEV), cnt.to(DEV)))
+        assert torch.equal(inverse == -1, is_pad)
+        assert torch.equal(uniq[inverse[~is_pad].long()], recv[~is_pad])
+        m = len(total) + 1  # the pads dedup into one entry
+        assert sorted(uniq[:m].tolist()) == sorted(total) + [pad_key]
+        assert bool((slots[m:] == -1).all())
+        for k, s in zip(uniq[:m].tolist(), slots[:m].tolist()):
+            assert (s >= 0) == (k != pad_key and total[k] >= 2)
+        # the owner pass bumps only the epoch: versions stay at the step
+        # the storage entered graph mode with
+        assert _entry_map(st_c) == {k: (f, 10) for k, f in total.items()}
+    pad = torch.tensor([pad_key])
+    assert int(st_c.frequencies(pad)[0]) == 0  # PAD_KEY: no metadata
+    assert int(st_c.versions(pad)[0]) == -1
+    for st in (st_a, st_b, st_c):
+        st._check_error()

@@ -126,26 +126,14 @@ def debug_lookup(ev, args, label=""):
     st._ensure_capacity(nnz)
     mark("ensure_cap")
     st._epoch += 1
-    uniq_buf = torch.empty(nnz, dtype=torch.int64, device=st.device)
-    centry_buf = torch.empty(nnz, dtype=torch.int64, device=st.device)
-    m_counter = torch.zeros(1, dtype=torch.int32, device=st.device)
-    mark("alloc")
-    st.ext.ht_dedup_a(keys, st.ht_keys, st.ht_freq, st.ht_version,
-                      st.ht_epoch, st.ht_compact, st._epoch, 0,
-                      st.entry_counter, m_counter, uniq_buf, centry_buf,
-                      st.error_flag)
-    mark("pass_a")
+    uniq_buf, centry_buf, occ_entry, m_counter = st._dedup_claim(keys)
+    mark("alloc+pass_a")
     c = torch.cat([m_counter, st.entry_counter, st.slot_counter]).cpu()
     m = int(c[0])
     mark("sync_m")
-    inverse, counts, rank = st.ext.ht_dedup_c(keys, st.ht_keys,
-                                              st.ht_compact, m)
+    inverse, counts, rank = st._dedup_count(occ_entry, m)
     mark("pass_c")
-    slots = st.ext.ht_dedup_b(
-        centry_buf[:m], uniq_buf[:m], st.ht_slot, st.ht_freq,
-        st.ht_version, counts, 0, st.slot_counter, st.max_slots,
-        st.values, st.default_values, st.dvd_per_table, st.key_bits,
-        st._init_limit(), st.filter_freq, st.error_flag)
+    slots = st._dedup_admit(centry_buf[:m], uniq_buf[:m], counts, step=0)
     mark("pass_b")
     cold_new = (slots >= st.hot_rows) & (slots >= max(st.hot_rows, prev))
     n_cold_new = int(cold_new.sum())
