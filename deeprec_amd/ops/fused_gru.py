@@ -25,7 +25,7 @@ class _FusedGRUFunction(torch.autograd.Function):
         B, T, D = x.shape
         H = w_hh.shape[1]
         x16 = x.reshape(B * T, D).to(torch.bfloat16).contiguous()
-        w_ih16 = w_ih.detach().to(torch.bfloat16)
+        w_ih16 = w_ih.detach().to(torch.bfloat16).contiguous()
         x3 = ext.linear_fwd(x16, w_ih16, b_ih.detach().float(), 0)
         u16 = w_hh.detach().to(torch.bfloat16).contiguous()
         bh = b_hh.detach().float()

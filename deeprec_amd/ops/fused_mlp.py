@@ -25,7 +25,7 @@ class _FusedLinear(torch.autograd.Function):
         # w16_cache: bf16 shadow refreshed once per optimizer step by
         # enable_weight_cache() — replaces a per-layer cast kernel
         w16 = (w16_cache if w16_cache is not None
-               else weight.detach().to(torch.bfloat16))
+               else weight.detach().to(torch.bfloat16).contiguous())
         x16 = x.to(torch.bfloat16).contiguous()
         out = ext.linear_fwd(x16, w16, bias.detach().float(), act_id)
         ctx.ext = ext

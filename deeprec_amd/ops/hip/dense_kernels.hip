@@ -28,6 +28,7 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <algorithm>
 #include <cstdint>
 
 namespace py = pybind11;
@@ -620,14 +621,25 @@ __global__ void k_l2norm_bwd(const short* __restrict__ dY,
 }
 
 // zero-fill (see ev_kernels k_zero_f32: memset nodes don't replay in
-// captured graphs)
+// captured graphs). p may be any 4-byte-aligned slice of a flat buffer
+// (FlatDenseAdam hands out [dW | db] slices back to back, so a slice
+// after an N = 1 layer starts at an odd element): a scalar head of up to
+// 3 floats brings the float4 body to 16-byte alignment, a scalar tail
+// finishes the slice.
 __global__ void k_zero_f32d(float* __restrict__ p, int64_t n) {
+  const int64_t to16 =
+      (int64_t)((16 - (reinterpret_cast<uintptr_t>(p) & 15)) & 15) >> 2;
+  const int64_t head = to16 < n ? to16 : n;
+  const int64_t nbody = (n - head) & ~3LL;
+  float* body = p + head;
   int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4;
   int64_t stride = gridDim.x * (int64_t)blockDim.x * 4;
-  for (; i + 3 < n; i += stride)
-    *reinterpret_cast<float4*>(p + i) = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (blockIdx.x == 0 && threadIdx.x == 0)
-    for (int64_t j = n & ~3LL; j < n; ++j) p[j] = 0.0f;
+  for (; i < nbody; i += stride)
+    *reinterpret_cast<float4*>(body + i) = make_float4(0.f, 0.f, 0.f, 0.f);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    for (int64_t j = 0; j < head; ++j) p[j] = 0.0f;
+    for (int64_t j = head + nbody; j < n; ++j) p[j] = 0.0f;
+  }
 }
 
 // ---------------------------------------------------------------------
@@ -1028,11 +1040,31 @@ static short* bf_ptr_mut(torch::Tensor& t) {
   return reinterpret_cast<short*>(t.data_ptr<at::BFloat16>());
 }
 
+// The kernels index their operands as dense row-major bf16 matrices; a
+// strided view or another dtype would be read as if it were one and
+// return numbers, so every wrapper rejects them before launching.
+static void check_bf16_matrix(const torch::Tensor& t, const char* op,
+                              const char* name) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on the GPU");
+  TORCH_CHECK(t.dim() == 2, op, ": ", name, " must be 2-D, got ", t.dim(),
+              "-D");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, op, ": ", name,
+              " must be bfloat16, got ", t.scalar_type());
+  TORCH_CHECK(t.is_contiguous(), op, ": ", name,
+              " must be contiguous (row-major)");
+}
+
 torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w_bf16,
                          torch::Tensor bias, int64_t act,
                          int64_t variant) {
-  TORCH_CHECK(x.scalar_type() == torch::kBFloat16 && x.is_contiguous());
+  check_bf16_matrix(x, "linear_fwd", "x");
+  check_bf16_matrix(w_bf16, "linear_fwd", "w");
+  TORCH_CHECK(x.size(1) == w_bf16.size(1), "linear_fwd: x is [M,",
+              x.size(1), "] but w is [N,", w_bf16.size(1), "]");
   int M = x.size(0), K = x.size(1), N = w_bf16.size(0);
+  TORCH_CHECK(!bias.defined() || bias.numel() == 0 ||
+                  (bias.numel() == N && bias.is_contiguous()),
+              "linear_fwd: bias must be empty or contiguous [N]");
   auto out = torch::empty({M, N}, x.options());
   int tiles_n = (N + 63) / 64;
   const float* bp =
@@ -1051,6 +1083,10 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w_bf16,
 }
 
 torch::Tensor linear_dx(torch::Tensor g, torch::Tensor w_bf16) {
+  check_bf16_matrix(g, "linear_dx", "g");
+  check_bf16_matrix(w_bf16, "linear_dx", "w");
+  TORCH_CHECK(g.size(1) == w_bf16.size(0), "linear_dx: g is [M,", g.size(1),
+              "] but w is [", w_bf16.size(0), ",K]");
   int M = g.size(0), N = g.size(1), K = w_bf16.size(1);
   auto dx = torch::empty({M, K}, g.options());
   int tiles_k = (K + 63) / 64;
@@ -1070,12 +1106,16 @@ torch::Tensor linear_dx(torch::Tensor g, torch::Tensor w_bf16) {
 static std::tuple<torch::Tensor, torch::Tensor> linear_dw_impl(
     torch::Tensor g, torch::Tensor x, torch::Tensor ws, bool want_bias,
     int64_t variant) {
+  check_bf16_matrix(g, "linear_dw", "g");
+  check_bf16_matrix(x, "linear_dw", "x");
+  TORCH_CHECK(g.size(0) == x.size(0), "linear_dw: g has ", g.size(0),
+              " rows but x has ", x.size(0));
   int M = g.size(0), N = g.size(1), K = x.size(1);
   // one fill-kernel zero for dW + dbias (cheaper than torch's fill
   // machinery; hipMemsetAsync is avoided: memset nodes recorded during
   // hipGraph capture were observed not to replay)
   int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
-  k_zero_f32d<<<(int)std::min<int64_t>((ws_len / 4 + 255) / 256, 1024),
+  k_zero_f32d<<<(int)std::clamp<int64_t>((ws_len / 4 + 255) / 256, 1, 1024),
                 256, 0, dense_stream()>>>(ws.data_ptr<float>(), ws_len);
   auto dw = ws.narrow(0, 0, (int64_t)N * K).view({N, K});
   auto db = want_bias ? ws.narrow(0, (int64_t)N * K, N) : torch::Tensor();
@@ -1107,6 +1147,8 @@ std::tuple<torch::Tensor, torch::Tensor> linear_dw(torch::Tensor g,
                                                    torch::Tensor x,
                                                    bool want_bias,
                                                    int64_t variant) {
+  check_bf16_matrix(g, "linear_dw", "g");
+  check_bf16_matrix(x, "linear_dw", "x");
   int N = g.size(1), K = x.size(1);
   int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
   auto ws = torch::empty({ws_len}, g.options().dtype(torch::kFloat32));
@@ -1123,6 +1165,8 @@ std::tuple<torch::Tensor, torch::Tensor> linear_dw_out(torch::Tensor g,
                                                        bool want_bias,
                                                        int64_t variant) {
   TORCH_CHECK(ws.is_contiguous() && ws.scalar_type() == torch::kFloat32);
+  check_bf16_matrix(g, "linear_dw_out", "g");
+  check_bf16_matrix(x, "linear_dw_out", "x");
   int N = g.size(1), K = x.size(1);
   int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
   TORCH_CHECK(ws.numel() == ws_len, "linear_dw_out: workspace size");
