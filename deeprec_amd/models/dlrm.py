@@ -51,6 +51,7 @@ class DLRM(nn.Module):
         # (measured 148us for 8192x512x13); zero-padding is math-identical
         self.dense_in = 16
         use_fused = bf16 and torch.device(device).type == "cuda"
+        self._fused = use_fused
         n_f = num_sparse + 1
         n_pairs = n_f * (n_f - 1) // 2
         # pad pair count to a multiple of 16 so the fused top-MLP GEMM gets
@@ -124,9 +125,8 @@ class DLRM(nn.Module):
         import contextlib
         amp = (torch.autocast(device_type="cuda", dtype=torch.bfloat16)
                if compute_dtype == torch.bfloat16 else contextlib.nullcontext())
-        if dense.shape[1] < self.dense_in:
-            dense = nn.functional.pad(
-                dense, (0, self.dense_in - dense.shape[1]))
+        from deeprec_amd.ops.fused_mlp import prep_dense
+        dense = prep_dense(dense, self.dense_in, fused=self._fused)
         with amp:
             bot = self.mlp_bot(dense)
             if self.interaction_op == "dot":

@@ -64,6 +64,15 @@ __device__ __forceinline__ short f2bf_u16(float f) {
   return (short)(cv.i >> 16);
 }
 
+// activation gradient of one element: g * act'(out), with out the saved
+// bf16 activation; act 1=relu, 2=sigmoid. Shared by k_act_bwd and the dX
+// epilogues so that the fused and the two-kernel forms agree bit for bit.
+__device__ __forceinline__ short act_grad_u16(short g, short o, int act) {
+  const float ov = bf2f_u16(o);
+  if (act == 1) return ov > 0.0f ? g : (short)0;
+  return f2bf_u16(bf2f_u16(g) * ov * (1.0f - ov));
+}
+
 // Load an 8-wide bf16 fragment row: src row-major [rows, cols], fragment
 // element i = src[r][k0 + i]; ZERO-FILLED outside bounds.
 __device__ __forceinline__ bf16x8 load_frag_row(const short* __restrict__ src,
@@ -197,10 +206,16 @@ __global__ void k_linear_fwd_t(const short* __restrict__ A,
 
 // ------------------------------------------------------------------
 // dX[M,K] = G[M,N] @ W[N,K]   (GEMM-K = N; B fragment is strided)
+// prev_out [M,K] (optional): the saved output of the layer that produced
+// this layer's input. When set, the epilogue stores
+// act_grad(bf16(acc), prev_out, prev_act) — the next dX/dW's G operand —
+// which removes that layer's k_act_bwd pass over dX.
 // ------------------------------------------------------------------
 __global__ void k_linear_dx(const short* __restrict__ G,
                             const short* __restrict__ W, int M, int N, int K,
-                            short* __restrict__ dX) {
+                            short* __restrict__ dX,
+                            const short* __restrict__ prev_out,
+                            int prev_act) {
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int ktiles64 = (K + 63) / 64;
@@ -232,7 +247,10 @@ __global__ void k_linear_dx(const short* __restrict__ G,
     for (int i = 0; i < 4; ++i) {
       int cm = m0 + (lane >> 4) * 4 + i;
       if (cm >= M) continue;
-      dX[(int64_t)cm * K + ck] = f2bf_u16(acc[t][i]);
+      short v = f2bf_u16(acc[t][i]);
+      if (prev_out)
+        v = act_grad_u16(v, prev_out[(int64_t)cm * K + ck], prev_act);
+      dX[(int64_t)cm * K + ck] = v;
     }
   }
 }
@@ -249,7 +267,9 @@ __global__ void k_linear_dx(const short* __restrict__ G,
 constexpr int DX_NSUP = 256;  // N rows staged per superchunk (33 KB LDS)
 __global__ void k_linear_dx_lds(const short* __restrict__ G,
                                 const short* __restrict__ W, int M, int N,
-                                int K, short* __restrict__ dX) {
+                                int K, short* __restrict__ dX,
+                                const short* __restrict__ prev_out,
+                                int prev_act) {
   __shared__ short wl[64][DX_NSUP + 8];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -308,7 +328,10 @@ __global__ void k_linear_dx_lds(const short* __restrict__ G,
       for (int i = 0; i < 4; ++i) {
         int cm = m0 + rg * 16 + (lane >> 4) * 4 + i;
         if (cm >= M) continue;
-        dX[(int64_t)cm * K + ck] = f2bf_u16(acc[rg][t][i]);
+        short v = f2bf_u16(acc[rg][t][i]);
+        if (prev_out)
+          v = act_grad_u16(v, prev_out[(int64_t)cm * K + ck], prev_act);
+        dX[(int64_t)cm * K + ck] = v;
       }
     }
   }
@@ -799,25 +822,47 @@ __global__ void k_act_bwd(const short* __restrict__ dY,
     bf16x8 o = *reinterpret_cast<const bf16x8*>(out + i);
     bf16x8 r;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      if (act == 1) {
-        r[j] = bf2f_u16(o[j]) > 0.0f ? g[j] : (short)0;
-      } else {
-        float ov = bf2f_u16(o[j]);
-        r[j] = f2bf_u16(bf2f_u16(g[j]) * ov * (1.0f - ov));
-      }
-    }
+    for (int j = 0; j < 8; ++j) r[j] = act_grad_u16(g[j], o[j], act);
     *reinterpret_cast<bf16x8*>(G + i) = r;
   }
   // tail
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    for (int64_t j = n & ~7LL; j < n; ++j) {
-      if (act == 1) {
-        G[j] = bf2f_u16(out[j]) > 0.0f ? dY[j] : (short)0;
-      } else {
-        float ov = bf2f_u16(out[j]);
-        G[j] = f2bf_u16(bf2f_u16(dY[j]) * ov * (1.0f - ov));
+    for (int64_t j = n & ~7LL; j < n; ++j)
+      G[j] = act_grad_u16(dY[j], out[j], act);
+  }
+}
+
+// dense-input preparation: fp32 [M,K] -> bf16 [M,KP] with a zero tail
+// (KP >= K), one pass in place of a pad kernel plus a cast kernel. One
+// thread per group of 8 output columns; NaN maps to the canonical quiet
+// NaN like torch's cast (f2bf_u16 alone would carry a low-mantissa NaN
+// into infinity).
+__global__ void k_pad_cast_bf16(const float* __restrict__ x, int64_t M, int K,
+                                int KP, short* __restrict__ y) {
+  const int gpr = (KP + 7) / 8;  // groups per row
+  const int64_t ngroups = M * gpr;
+  int64_t gi = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; gi < ngroups; gi += stride) {
+    const int64_t r = gi / gpr;
+    const int c0 = (int)(gi % gpr) * 8;
+    bf16x8 v;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      short b = 0;
+      if (c0 + j < K) {
+        const float f = x[r * K + c0 + j];
+        b = f != f ? (short)0x7fc0 : f2bf_u16(f);
       }
+      v[j] = b;
+    }
+    short* dst = y + r * KP + c0;
+    if ((KP & 7) == 0) {
+      *reinterpret_cast<bf16x8*>(dst) = v;
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (c0 + j < KP) dst[j] = v[j];
     }
   }
 }
@@ -1082,30 +1127,56 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w_bf16,
   return out;
 }
 
-torch::Tensor linear_dx(torch::Tensor g, torch::Tensor w_bf16) {
+// prev_out/prev_act: fuse the previous layer's activation gradient into
+// the epilogue — the result equals act_bwd(linear_dx(g, w), prev_out,
+// prev_act) bit for bit. prev_act == 0 leaves dX plain.
+torch::Tensor linear_dx(torch::Tensor g, torch::Tensor w_bf16,
+                        c10::optional<torch::Tensor> prev_out,
+                        int64_t prev_act) {
   check_bf16_matrix(g, "linear_dx", "g");
   check_bf16_matrix(w_bf16, "linear_dx", "w");
   TORCH_CHECK(g.size(1) == w_bf16.size(0), "linear_dx: g is [M,", g.size(1),
               "] but w is [", w_bf16.size(0), ",K]");
   int M = g.size(0), N = g.size(1), K = w_bf16.size(1);
+  TORCH_CHECK(prev_act >= 0 && prev_act <= 2, "linear_dx: prev_act must be "
+              "0 (none), 1 (relu) or 2 (sigmoid), got ", prev_act);
+  const short* pp = nullptr;
+  if (prev_out.has_value()) {
+    check_bf16_matrix(*prev_out, "linear_dx", "prev_out");
+    TORCH_CHECK(prev_out->size(0) == M && prev_out->size(1) == K,
+                "linear_dx: prev_out is [", prev_out->size(0), ",",
+                prev_out->size(1), "] but dX is [", M, ",", K, "]");
+    if (prev_act != 0) pp = bf_ptr(*prev_out);
+  } else {
+    TORCH_CHECK(prev_act == 0, "linear_dx: prev_act without prev_out");
+  }
   auto dx = torch::empty({M, K}, g.options());
   int tiles_k = (K + 63) / 64;
   if (N >= 128) {
     // wide GEMM-K: strided W-column loads dominate -> LDS-staged variant
     int blocks = ((M + 127) / 128) * tiles_k;
     k_linear_dx_lds<<<blocks, 256, 0, dense_stream()>>>(
-        bf_ptr(g), bf_ptr(w_bf16), M, N, K, bf_ptr_mut(dx));
+        bf_ptr(g), bf_ptr(w_bf16), M, N, K, bf_ptr_mut(dx), pp,
+        (int)prev_act);
   } else {
     int blocks = ((M + 63) / 64) * tiles_k;
     k_linear_dx<<<blocks, 256, 0, dense_stream()>>>(
-        bf_ptr(g), bf_ptr(w_bf16), M, N, K, bf_ptr_mut(dx));
+        bf_ptr(g), bf_ptr(w_bf16), M, N, K, bf_ptr_mut(dx), pp,
+        (int)prev_act);
   }
   return dx;
 }
 
+static void zero_f32_launch(float* p, int64_t n) {
+  k_zero_f32d<<<(int)std::clamp<int64_t>((n / 4 + 255) / 256, 1, 1024), 256,
+                0, dense_stream()>>>(p, n);
+}
+
+// zero = false: the caller has cleared ws already (one zero_f32 over a
+// whole tower's adjacent slices); the kernels only accumulate.
 static std::tuple<torch::Tensor, torch::Tensor> linear_dw_impl(
     torch::Tensor g, torch::Tensor x, torch::Tensor ws, bool want_bias,
-    int64_t variant) {
+    int64_t variant, bool zero = true) {
   check_bf16_matrix(g, "linear_dw", "g");
   check_bf16_matrix(x, "linear_dw", "x");
   TORCH_CHECK(g.size(0) == x.size(0), "linear_dw: g has ", g.size(0),
@@ -1115,8 +1186,7 @@ static std::tuple<torch::Tensor, torch::Tensor> linear_dw_impl(
   // machinery; hipMemsetAsync is avoided: memset nodes recorded during
   // hipGraph capture were observed not to replay)
   int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
-  k_zero_f32d<<<(int)std::clamp<int64_t>((ws_len / 4 + 255) / 256, 1, 1024),
-                256, 0, dense_stream()>>>(ws.data_ptr<float>(), ws_len);
+  if (zero) zero_f32_launch(ws.data_ptr<float>(), ws_len);
   auto dw = ws.narrow(0, 0, (int64_t)N * K).view({N, K});
   auto db = want_bias ? ws.narrow(0, (int64_t)N * K, N) : torch::Tensor();
   int m_chunks = (M + 127) / 128;
@@ -1163,14 +1233,44 @@ std::tuple<torch::Tensor, torch::Tensor> linear_dw_out(torch::Tensor g,
                                                        torch::Tensor x,
                                                        torch::Tensor ws,
                                                        bool want_bias,
-                                                       int64_t variant) {
-  TORCH_CHECK(ws.is_contiguous() && ws.scalar_type() == torch::kFloat32);
+                                                       int64_t variant,
+                                                       bool zero) {
+  TORCH_CHECK(ws.is_cuda() && ws.is_contiguous() &&
+              ws.scalar_type() == torch::kFloat32);
   check_bf16_matrix(g, "linear_dw_out", "g");
   check_bf16_matrix(x, "linear_dw_out", "x");
   int N = g.size(1), K = x.size(1);
   int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
   TORCH_CHECK(ws.numel() == ws_len, "linear_dw_out: workspace size");
-  return linear_dw_impl(g, x, ws, want_bias, variant);
+  return linear_dw_impl(g, x, ws, want_bias, variant, zero);
+}
+
+// clear any contiguous fp32 1-D tensor with the capture-safe fill kernel
+void zero_f32(torch::Tensor ws) {
+  TORCH_CHECK(ws.is_cuda() && ws.dim() == 1 && ws.is_contiguous() &&
+                  ws.scalar_type() == torch::kFloat32,
+              "zero_f32: ws must be a contiguous 1-D fp32 GPU tensor");
+  if (ws.numel() == 0) return;
+  zero_f32_launch(ws.data_ptr<float>(), ws.numel());
+}
+
+// x fp32 [M,K] -> bf16 [M,k_pad], columns K.. zero; rounding as torch's
+// fp32 -> bf16 cast (nearest even)
+torch::Tensor pad_cast_bf16(torch::Tensor x, int64_t k_pad) {
+  TORCH_CHECK(x.is_cuda() && x.dim() == 2 && x.is_contiguous() &&
+                  x.scalar_type() == torch::kFloat32,
+              "pad_cast_bf16: x must be a contiguous 2-D fp32 GPU tensor");
+  int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(k_pad >= K, "pad_cast_bf16: k_pad ", k_pad, " < K ", K);
+  TORCH_CHECK(k_pad < (1 << 30), "pad_cast_bf16: k_pad ", k_pad,
+              " is out of range (< 2^30)");
+  auto y = torch::empty({M, k_pad}, x.options().dtype(torch::kBFloat16));
+  if (M == 0 || k_pad == 0) return y;
+  int64_t groups = M * ((k_pad + 7) / 8);
+  int blocks = (int)std::clamp<int64_t>((groups + 255) / 256, 1, 4096);
+  k_pad_cast_bf16<<<blocks, 256, 0, dense_stream()>>>(
+      x.data_ptr<float>(), M, (int)K, (int)k_pad, bf_ptr_mut(y));
+  return y;
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> resln_fwd(
@@ -1343,11 +1443,15 @@ void register_dense(py::module_& mod) {
   mod.def("interact_cat_bwd", &interact_cat_bwd);
   mod.def("linear_fwd", &linear_fwd, py::arg("x"), py::arg("w"),
           py::arg("bias"), py::arg("act"), py::arg("variant") = -1);
-  mod.def("linear_dx", &linear_dx);
+  mod.def("linear_dx", &linear_dx, py::arg("g"), py::arg("w"),
+          py::arg("prev_out") = py::none(), py::arg("prev_act") = 0);
   mod.def("linear_dw", &linear_dw, py::arg("g"), py::arg("x"),
           py::arg("want_bias"), py::arg("variant") = -1);
   mod.def("linear_dw_out", &linear_dw_out, py::arg("g"), py::arg("x"),
-          py::arg("ws"), py::arg("want_bias"), py::arg("variant") = -1);
+          py::arg("ws"), py::arg("want_bias"), py::arg("variant") = -1,
+          py::arg("zero") = true);
+  mod.def("zero_f32", &zero_f32, py::arg("ws"));
+  mod.def("pad_cast_bf16", &pad_cast_bf16, py::arg("x"), py::arg("k_pad"));
   mod.def("dense_adam", &dense_adam);
   mod.def("resln_fwd", &resln_fwd);
   mod.def("resln_bwd", &resln_bwd);
