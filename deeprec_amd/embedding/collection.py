@@ -151,16 +151,13 @@ class EmbeddingCollection:
         if not train:
             return self._forward(uniq, slots, inverse, offsets_cat,
                                  weights_cat, batch, out_dtype)
-        order, bounds, chunk_u, chunk_k0 = self._prep_backward(inverse,
-                                                               counts)
+        order, bounds = self._prep_backward(inverse, counts)
         row_coeff = self._row_coeffs(offsets_cat, row_ids_cat, weights_cat,
                                      batch)
         return _CollectionLookup.apply(
             self._anchor, self, uniq, slots, inverse, offsets_cat,
-            row_ids_cat, order, bounds, chunk_u, chunk_k0, row_coeff,
-            weights_cat, batch, out_dtype, False)
-
-    _CHUNK = 128
+            row_ids_cat, order, bounds, row_coeff, weights_cat, batch,
+            out_dtype, False)
 
     def _dedup_and_probe(self, values_cat, train):
         """unique + single hash probe. GPU training uses the fused hash
@@ -183,9 +180,9 @@ class EmbeddingCollection:
         return uniq, inverse.to(torch.int32), counts, slots
 
     def _prep_backward(self, inverse, counts):
-        """CSR over unique keys + fixed-size occurrence chunks so the
-        backward is balanced under zipf-hot keys (no 10k-iteration
-        threads)."""
+        """CSR over unique keys: `order` lists the occurrences sorted by
+        unique row, which is what the occurrence-balanced backward
+        walks."""
         m = counts.numel()
         dev = self.device
         c32 = counts.to(torch.int32)
@@ -193,7 +190,7 @@ class EmbeddingCollection:
         bounds[1:] = c32.cumsum(0)
         if self.device.type != "cuda":
             order = torch.argsort(inverse.long()).to(torch.int32)
-            return order, bounds, None, None
+            return order, bounds
         # sort-free CSR build; when the fused dedup ran, pass C already
         # recorded each occurrence's rank within its key, so order is a
         # direct scatter (no second atomic-cursor pass over nnz)
@@ -204,7 +201,7 @@ class EmbeddingCollection:
                 inverse, rank, bounds, self.storage.error_flag)
         else:  # torch.unique (sort) path
             order = self.storage.ext.csr_order(inverse, bounds, m)
-        return order, bounds, None, None
+        return order, bounds
 
     def lookup_matrix(self, ids: torch.Tensor, out_dtype=None,
                       train: bool = True) -> torch.Tensor:
@@ -237,12 +234,11 @@ class EmbeddingCollection:
         if not train:
             return self._forward(uniq, slots, inverse, cache["offsets"],
                                  None, batch, out_dtype)
-        order, bounds, chunk_u, chunk_k0 = self._prep_backward(inverse,
-                                                               counts)
+        order, bounds = self._prep_backward(inverse, counts)
         return _CollectionLookup.apply(
             self._anchor, self, uniq, slots, inverse, cache["offsets"],
-            cache["row_ids"], order, bounds, chunk_u, chunk_k0,
-            cache["row_coeff"], None, batch, out_dtype, True)
+            cache["row_ids"], order, bounds, cache["row_coeff"], None,
+            batch, out_dtype, True)
 
     def _forward(self, uniq, slots, inverse, offsets_cat, weights_cat, batch,
                  out_dtype, emb_override=None):
@@ -289,23 +285,19 @@ class EmbeddingCollection:
             outs.append(out_t)
         return torch.cat(outs, dim=1)  # [B, N*D], table-major inner
 
-    def _backward(self, grad_out, order, bounds, chunk_u, chunk_k0,
-                  row_ids_cat, weights_cat, row_coeff, m, batch,
-                  identity_rows=False):
+    def _backward(self, grad_out, order, bounds, inverse, row_ids_cat,
+                  weights_cat, row_coeff, m, batch, identity_rows=False):
+        """grad_unique [m, dim]. `inverse` is the occurrence -> unique-row
+        map `order` was built from (the GPU kernel walks occurrences and
+        needs no bounds; the CPU reference uses bounds)."""
         if self.device.type == "cuda":
-            m_dev = (self.storage._last_m_dev
-                     if self.graph_mode else torch.Tensor())
-            # zipf batches (nnz >> m) want hot-key splitting; mostly-
-            # unique batches want 1 split (8x fewer idle probes)
-            nnz = row_ids_cat.numel()
-            # under capture m is nnz-padded, so the ratio test is wrong
-            # there; captured workloads are the zipf ones -> split
-            splits = 32 if (self.graph_mode or nnz > 2 * m) else 1
-            return self.storage.ext.group_pooled_bwd_strided(
-                grad_out.contiguous(), order, bounds, row_ids_cat,
+            # occurrence-balanced: cost depends on nnz only, so neither
+            # key skew nor an nnz-padded m (graph capture) changes it
+            return self.storage.ext.group_pooled_bwd_seg(
+                grad_out.contiguous(), order, inverse, row_ids_cat,
                 weights_cat if weights_cat is not None else torch.Tensor(),
-                row_coeff, m, m_dev, batch, self.n_tables, self.dim,
-                identity_rows, splits)
+                row_coeff, m, batch, self.n_tables, self.dim,
+                identity_rows, 0)
         # CPU reference path
         g = grad_out.float().reshape(batch, self.n_tables, self.dim)
         grad_unique = torch.zeros(m, self.dim)
@@ -380,28 +372,26 @@ class EmbeddingCollection:
 class _CollectionLookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, coll, uniq, slots, inverse, offsets_cat,
-                row_ids_cat, order, bounds, chunk_u, chunk_k0, row_coeff,
-                weights_cat, batch, out_dtype, identity_rows=False):
+                row_ids_cat, order, bounds, row_coeff, weights_cat, batch,
+                out_dtype, identity_rows=False):
         out = coll._forward(uniq, slots, inverse, offsets_cat, weights_cat,
                             batch, out_dtype)
         ctx.coll = coll
         ctx.batch = batch
         ctx.identity_rows = identity_rows
-        ctx.save_for_backward(uniq, slots, order, bounds, row_ids_cat,
-                              row_coeff)
-        ctx.chunks = (chunk_u, chunk_k0)
+        ctx.save_for_backward(uniq, slots, order, bounds, inverse,
+                              row_ids_cat, row_coeff)
         ctx.weights_cat = weights_cat
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        uniq, slots, order, bounds, row_ids_cat, row_coeff = ctx.saved_tensors
+        uniq, slots, order, bounds, inverse, row_ids_cat, row_coeff = \
+            ctx.saved_tensors
         coll = ctx.coll
-        chunk_u, chunk_k0 = ctx.chunks
-        grad_unique = coll._backward(grad_out, order, bounds, chunk_u,
-                                     chunk_k0, row_ids_cat,
-                                     ctx.weights_cat, row_coeff,
-                                     uniq.numel(), ctx.batch,
+        grad_unique = coll._backward(grad_out, order, bounds, inverse,
+                                     row_ids_cat, ctx.weights_cat,
+                                     row_coeff, uniq.numel(), ctx.batch,
                                      ctx.identity_rows)
         coll.accumulate_grad(slots, uniq, grad_unique)
-        return (torch.zeros_like(coll._anchor),) + (None,) * 15
+        return (torch.zeros_like(coll._anchor),) + (None,) * 13

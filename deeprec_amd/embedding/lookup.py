@@ -67,7 +67,6 @@ class _PooledLookup(torch.autograd.Function):
 
 
 _COMBINER_ID = {"sum": 0, "mean": 1, "sqrtn": 2}
-_CHUNK = 128
 
 
 def _chunked_ev_backward(ev, grad_out, inverse, offsets, row_ids, counts,
@@ -95,13 +94,11 @@ def _chunked_ev_backward(ev, grad_out, inverse, offsets, row_ids, counts,
         row_coeff = torch.where(lengths > 0,
                                 1.0 / denom.clamp(min=1e-12),
                                 torch.zeros_like(lengths))
-    nnz = inverse.numel()
-    splits = 32 if nnz > 2 * m else 1
-    return ext.group_pooled_bwd_strided(
-        grad_out.contiguous(), order, bounds, row_ids.to(torch.int32),
+    return ext.group_pooled_bwd_seg(
+        grad_out.contiguous(), order, inverse.to(torch.int32),
+        row_ids.to(torch.int32),
         weights.float() if weights is not None else torch.Tensor(),
-        row_coeff, m, torch.Tensor(), offsets.numel() - 1, 1, ev.dim,
-        False, splits)
+        row_coeff, m, offsets.numel() - 1, 1, ev.dim, False, 0)
 
 
 def _drop_positions(sp_ids: RaggedIds, keep: torch.Tensor) -> RaggedIds:

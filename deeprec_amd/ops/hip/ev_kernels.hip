@@ -495,6 +495,64 @@ __global__ void k_rows_to_padded(const float* __restrict__ src,
   }
 }
 
+// Wave-level grouping of equal values: zipf-hot keys put many equal keys
+// into one wave (the hottest DLRM key fills ~19 of 64 lanes of every wave
+// of its table), and per-occurrence atomics on them form one serial chain
+// per key. Pass C merges a wave's duplicates in registers and lets one
+// leader lane per distinct value touch memory.
+struct WaveGroup {
+  uint64_t mask;  // valid lanes of this wave holding the same value
+  int leader;     // lowest lane of mask
+  int pos;        // this lane's position inside mask
+};
+
+// Registers only (ballots and one shuffle per 8 rounds, no memory
+// operation). Must be called by the WHOLE wave, converged; lanes with
+// valid == false get mask 0 / leader 0 / pos 0.
+//
+// One ballot per value BIT splits the lanes into classes agreeing on the
+// bits seen so far. Classes only ever split, and equal values share every
+// bit, so as soon as every lane equals the lowest lane of its class the
+// classes are exactly the groups of equal values. With values whose low
+// bits are spread (hash-table entries) that holds after ~2*log2(64) bits
+// whether the wave holds 64 distinct values or one hot one; a loop that
+// retires one distinct value per round needs 64 rounds on all-distinct
+// input, which doubled pass C's time there.
+DEV_INLINE WaveGroup wave_group_by(uint64_t v, bool valid) {
+  WaveGroup g{0ull, 0, 0};
+  const int lane = __lane_id();
+  uint64_t mask = __ballot(valid);
+  int leader = lane;
+  for (int b = 0; b < 64; b += 8) {  // wave-uniform trip count
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const bool bit = (v >> (b + i)) & 1ull;
+      const uint64_t with = __ballot(bit);
+      mask &= bit ? with : ~with;  // a valid lane always keeps its own bit
+    }
+    leader = valid ? __ffsll((unsigned long long)mask) - 1 : lane;
+    const uint64_t lv = __shfl(v, leader);
+    if (!__ballot(valid && lv != v)) break;  // every class is one value
+  }
+  if (valid) {
+    g.mask = mask;
+    g.leader = leader;
+    g.pos = __popcll(mask & ((1ull << lane) - 1ull));
+  }
+  return g;
+}
+
+// First element of this wave's 64-wide slice and the grid's slice stride,
+// both wave-uniform, so a caller's grid-stride loop keeps every lane of the
+// wave in the loop (tail lanes are predicated, never exit early).
+DEV_INLINE int64_t wave_slice_begin() {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  return (blockIdx.x * (int64_t)(blockDim.x >> 6) + wave) * 64;
+}
+DEV_INLINE int64_t wave_slice_stride() {
+  return gridDim.x * (int64_t)(blockDim.x >> 6) * 64;
+}
+
 // Pass C (per occurrence): inverse + exact per-batch counts. Index-direct:
 // pass A recorded each occurrence's hash entry, so inverse/rank need NO
 // re-probe of the table (the probe was ~half of the dedup cost at 213k
@@ -506,20 +564,31 @@ __global__ void k_dedup_pass_c(
     int nnz, const int32_t* __restrict__ ht_compact,
     int32_t* __restrict__ inverse, int32_t* __restrict__ counts,
     int32_t* __restrict__ rank) {
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; j < nnz; j += stride) {
-    if (keys && keys[j] == PAD_KEY) {
-      inverse[j] = -1;
-      rank[j] = 0;
-      continue;
+  const int lane = __lane_id();
+  const int64_t stride = wave_slice_stride();
+  for (int64_t j0 = wave_slice_begin(); j0 < nnz; j0 += stride) {
+    const int64_t j = j0 + lane;
+    const bool in_range = j < nnz;
+    const bool valid = in_range && !(keys && keys[j] == PAD_KEY);
+    const int64_t entry = valid ? occ_entry[j] : 0;
+    // a wave's occurrences of one key share ONE returning atomic (a hot
+    // key's per-occurrence adds were a serial chain on one word); all
+    // leaders of the wave issue theirs in the same instruction
+    const WaveGroup g = wave_group_by((uint64_t)entry, valid);
+    int c = -1, base = 0;
+    if (valid && lane == g.leader) {
+      c = ht_compact[entry];
+      base = atomicAdd(&counts[c], __popcll(g.mask));
     }
-    int c = ht_compact[occ_entry[j]];
-    inverse[j] = c;
-    // the counter value doubles as this occurrence's rank within its
-    // key, letting the CSR order build become a direct scatter
-    // (k_csr_scatter) instead of a second atomic-cursor pass
-    rank[j] = atomicAdd(&counts[c], 1);
+    c = __shfl(c, g.leader);
+    base = __shfl(base, g.leader);
+    if (in_range) {
+      inverse[j] = valid ? c : -1;
+      // the counter value doubles as this occurrence's rank within its
+      // key, letting the CSR order build become a direct scatter
+      // (k_csr_scatter) instead of a second atomic-cursor pass
+      rank[j] = valid ? base + g.pos : 0;
+    }
   }
 }
 
@@ -827,52 +896,91 @@ __global__ void k_group_pooled_fwd(
   }
 }
 
+// Balanced segmented grad scatter. Work is split over OCCURRENCES in
+// sorted (CSR) order, not over unique keys: a group of LANES lanes (one
+// lane per embedding column, d += LANES for wider rows) owns R consecutive
+// positions k of `order`, so work per thread is constant whatever the key
+// skew and nothing runs for padded unique rows. All R gradient loads are
+// issued before the first add; runs of equal u = inverse[order[k]] are
+// summed in registers. A run that lies wholly inside the group (checked
+// against the neighbouring positions' u) stores plainly; a run cut by a
+// group edge adds atomically into the zero-filled output.
 // IDENTITY: the matrix fast path (one id per table per sample) has
 // row_ids == arange and unit combiner coefficients — skip both reads.
-template <typename GradT, int SPLITS, int CHUNK, bool IDENTITY>
-__global__ void k_group_pooled_bwd_strided(
+// Corrupt indices (order/inverse/row id out of range) are skipped, never
+// dereferenced.
+template <typename GradT, int LANES, int R, bool IDENTITY>
+__global__ void k_group_pooled_bwd_seg(
     const GradT* __restrict__ grad_out, const int32_t* __restrict__ order,
-    const int32_t* __restrict__ bounds, const int32_t* __restrict__ row_ids,
+    const int32_t* __restrict__ inverse, const int32_t* __restrict__ row_ids,
     const float* __restrict__ weights, const float* __restrict__ row_coeff,
-    int m, const int32_t* __restrict__ m_dev, int batch, int n_tables,
-    int dim, float* __restrict__ grad_unique) {
-  if (m_dev) m = *m_dev;  // graph capture: true unique count on device
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)m * dim * SPLITS;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; t < total; t += stride) {
-    int d = (int)(t % dim);
-    int64_t ud = t / dim;
-    int u = (int)(ud % m);
-    int s = (int)(ud / m);
-    int beg = bounds[u], end = bounds[u + 1];
-    int cnt = end - beg;
-    if (s * CHUNK >= cnt) continue;   // this split has no window
-    float acc = 0.0f;
-    for (int k0 = beg + s * CHUNK; k0 < end; k0 += SPLITS * CHUNK) {
-      int k1 = min(k0 + CHUNK, end);
-      for (int k = k0; k < k1; ++k) {
-        int j = order[k];
-        int rid = IDENTITY ? j : row_ids[j];
-        int table = rid / batch;
-        int b = rid % batch;
-        float g;
-        int64_t gidx = ((int64_t)b * n_tables + table) * dim + d;
-        if constexpr (std::is_same_v<GradT, __hip_bfloat16>)
-          g = bf2f(grad_out[gidx]);
-        else
-          g = grad_out[gidx];
-        if constexpr (IDENTITY) {
-          acc += g;
-        } else {
-          float w = weights ? weights[j] : 1.0f;
-          acc += w * row_coeff[rid] * g;
-        }
+    int nnz, int m_rows, int batch, int n_tables, int dim,
+    float* __restrict__ grad_unique) {
+  constexpr int kGroups = kBlock / LANES;  // groups per block
+  const int l = threadIdx.x % LANES;
+  const int64_t step = gridDim.x * (int64_t)kGroups * R;
+  const int n_rows = batch * n_tables;
+  auto u_at = [&](int64_t k) -> int {
+    if (k < 0 || k >= nnz) return -2;
+    int j = order[k];
+    if ((unsigned)j >= (unsigned)nnz) return -1;
+    int u = inverse[j];
+    return (unsigned)u < (unsigned)m_rows ? u : -1;
+  };
+  for (int64_t k0 = (blockIdx.x * (int64_t)kGroups + threadIdx.x / LANES) * R;
+       k0 < nnz; k0 += step) {
+    int u[R], grow[R];
+    float cf[R];
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      u[r] = -2;
+      grow[r] = 0;
+      cf[r] = 1.0f;
+      const int64_t k = k0 + r;
+      if (k < nnz) {
+        const int j = order[k];
+        if ((unsigned)j >= (unsigned)nnz) { u[r] = -1; continue; }
+        const int rid = IDENTITY ? j : row_ids[j];
+        const int uu = inverse[j];
+        if ((unsigned)uu >= (unsigned)m_rows ||
+            (unsigned)rid >= (unsigned)n_rows) { u[r] = -1; continue; }
+        u[r] = uu;
+        grow[r] = (rid % batch) * n_tables + rid / batch;
+        if constexpr (!IDENTITY)
+          cf[r] = (weights ? weights[j] : 1.0f) * row_coeff[rid];
       }
     }
-    int64_t o = (int64_t)u * dim + d;
-    if (cnt <= CHUNK) grad_unique[o] = acc;   // single window: plain store
-    else atomicAdd(&grad_unique[o], acc);
+    const int u_prev = u_at(k0 - 1);
+    const int u_next = u_at(k0 + R);
+    for (int d = l; d < dim; d += LANES) {
+      float g[R];
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        g[r] = 0.0f;
+        if (u[r] >= 0) {
+          const int64_t gidx = (int64_t)grow[r] * dim + d;
+          if constexpr (std::is_same_v<GradT, __hip_bfloat16>)
+            g[r] = bf2f(grad_out[gidx]);
+          else
+            g[r] = grad_out[gidx];
+        }
+      }
+      float acc = 0.0f;
+      bool cut = u[0] >= 0 && u_prev == u[0];  // run began in the group before
+#pragma unroll
+      for (int r = 0; r < R; ++r) {
+        if (u[r] < 0) continue;
+        if constexpr (IDENTITY) acc += g[r];
+        else acc += cf[r] * g[r];
+        const int un = (r + 1 < R) ? u[r + 1] : u_next;
+        if (un == u[r] && r + 1 < R) continue;  // run goes on in this group
+        float* dst = &grad_unique[(int64_t)u[r] * dim + d];
+        if (cut || un == u[r]) atomicAdd(dst, acc);
+        else *dst = acc;
+        acc = 0.0f;
+        cut = false;
+      }
+    }
   }
 }
 
@@ -1534,84 +1642,112 @@ torch::Tensor group_pooled_fwd_direct(
   return out;
 }
 
-template <typename T, int SPL, int CHUNK = 128>
-static void launch_bwd_strided(const T* gp, torch::Tensor& order,
-                               torch::Tensor& bounds, torch::Tensor& row_ids,
-                               const float* wptr, torch::Tensor& row_coeff,
-                               int64_t m, const int32_t* mdp, int64_t batch,
-                               int64_t n_tables, int64_t dim,
-                               bool identity_rows, torch::Tensor& out,
-                               hipStream_t stream) {
-  // grid-stride kernel: cap the grid so an nnz-padded m (graph capture)
-  // costs no extra block launches
-  int64_t total = std::min<int64_t>(m * dim * SPL, (int64_t)4096 * kBlock);
+// Positions of `order` per lane group in k_group_pooled_bwd_seg. From the
+// {4, 8, 16, 32} sweep (profiles/PERF_LOG.md): 16 is 10 % faster on the
+// zipf DLRM batch but needs 107 VGPRs (occupancy 4) and is 35 % slower on
+// all-distinct keys; 8 (56 VGPRs, occupancy 8) is never slower than the
+// kernel this one replaced; 32 spills.
+static constexpr int kSegR = 8;
+
+template <typename T, int LANES, int R>
+static void launch_bwd_seg(const T* gp, torch::Tensor& order,
+                           torch::Tensor& inverse, torch::Tensor& row_ids,
+                           const float* wptr, torch::Tensor& row_coeff,
+                           int64_t m, int64_t batch, int64_t n_tables,
+                           int64_t dim, bool identity_rows,
+                           torch::Tensor& out, hipStream_t stream) {
+  int64_t nnz = order.numel();
+  int64_t groups = (nnz + R - 1) / R;
+  int grid = n_blocks(groups * LANES);
   if (identity_rows) {
-    k_group_pooled_bwd_strided<T, SPL, CHUNK, true>
-        <<<n_blocks(total), kBlock, 0, stream>>>(
-            gp, order.data_ptr<int32_t>(), bounds.data_ptr<int32_t>(),
-            row_ids.data_ptr<int32_t>(), wptr, row_coeff.data_ptr<float>(),
-            (int)m, mdp, (int)batch, (int)n_tables, (int)dim,
-            out.data_ptr<float>());
+    k_group_pooled_bwd_seg<T, LANES, R, true><<<grid, kBlock, 0, stream>>>(
+        gp, order.data_ptr<int32_t>(), inverse.data_ptr<int32_t>(), nullptr,
+        nullptr, nullptr, (int)nnz, (int)m, (int)batch, (int)n_tables,
+        (int)dim, out.data_ptr<float>());
   } else {
-    k_group_pooled_bwd_strided<T, SPL, CHUNK, false>
-        <<<n_blocks(total), kBlock, 0, stream>>>(
-            gp, order.data_ptr<int32_t>(), bounds.data_ptr<int32_t>(),
-            row_ids.data_ptr<int32_t>(), wptr, row_coeff.data_ptr<float>(),
-            (int)m, mdp, (int)batch, (int)n_tables, (int)dim,
-            out.data_ptr<float>());
+    k_group_pooled_bwd_seg<T, LANES, R, false><<<grid, kBlock, 0, stream>>>(
+        gp, order.data_ptr<int32_t>(), inverse.data_ptr<int32_t>(),
+        row_ids.data_ptr<int32_t>(), wptr, row_coeff.data_ptr<float>(),
+        (int)nnz, (int)m, (int)batch, (int)n_tables, (int)dim,
+        out.data_ptr<float>());
   }
 }
 
-torch::Tensor group_pooled_bwd_strided(
-    torch::Tensor grad_out, torch::Tensor order, torch::Tensor bounds,
+template <typename T, int LANES>
+static void launch_bwd_seg_r(int64_t r, const T* gp, torch::Tensor& order,
+                             torch::Tensor& inverse, torch::Tensor& row_ids,
+                             const float* wptr, torch::Tensor& row_coeff,
+                             int64_t m, int64_t batch, int64_t n_tables,
+                             int64_t dim, bool identity_rows,
+                             torch::Tensor& out, hipStream_t stream) {
+#define SEG_CASE(RR)                                                       \
+  case RR:                                                                 \
+    launch_bwd_seg<T, LANES, RR>(gp, order, inverse, row_ids, wptr,        \
+                                 row_coeff, m, batch, n_tables, dim,       \
+                                 identity_rows, out, stream);              \
+    break;
+  switch (r) {
+    SEG_CASE(4)
+    SEG_CASE(8)
+    SEG_CASE(16)
+    SEG_CASE(32)
+    default:
+      TORCH_CHECK(false, "group_pooled_bwd_seg: r must be 4, 8, 16 or 32");
+  }
+#undef SEG_CASE
+}
+
+// grad_unique [m, dim] fp32 from the pooled output grad. `order` is the
+// CSR occurrence order, `inverse` maps an occurrence to its unique row;
+// r <= 0 selects the committed kSegR (other values exist for the sweep in
+// tools/scatter_sweep.py). m may be nnz-padded (graph capture): rows
+// beyond the true unique count are never referenced and stay zero.
+torch::Tensor group_pooled_bwd_seg(
+    torch::Tensor grad_out, torch::Tensor order, torch::Tensor inverse,
     torch::Tensor row_ids, torch::Tensor weights, torch::Tensor row_coeff,
-    int64_t m, torch::Tensor m_dev, int64_t batch, int64_t n_tables,
-    int64_t dim, bool identity_rows, int64_t splits) {
-  // splits: 8 for duplication-heavy (zipf) batches — hot keys fan out
-  // across concurrent accumulators; 1 for mostly-unique batches (long
-  // sequences) where extra splits are 8x wasted bounds probes.
+    int64_t m, int64_t batch, int64_t n_tables, int64_t dim,
+    bool identity_rows, int64_t r) {
   auto grad_unique = torch::empty(
       {m, dim}, grad_out.options().dtype(torch::kFloat32));
   if (m * dim == 0) return grad_unique;
+  TORCH_CHECK(inverse.numel() == order.numel(),
+              "group_pooled_bwd_seg: inverse/order size mismatch");
+  TORCH_CHECK(grad_out.numel() == batch * n_tables * dim,
+              "group_pooled_bwd_seg: grad_out is not [batch, n_tables*dim]");
+  if (!identity_rows)
+    TORCH_CHECK(row_ids.numel() == order.numel() &&
+                    row_coeff.numel() == batch * n_tables,
+                "group_pooled_bwd_seg: row_ids/row_coeff size mismatch");
   auto stream = current_stream();
   zero_fill(grad_unique.data_ptr<float>(), m * dim, stream);
+  if (order.numel() == 0) return grad_unique;
   const float* wptr =
       weights.defined() && weights.numel() ? weights.data_ptr<float>()
                                            : nullptr;
-  const int32_t* mdp =
-      m_dev.defined() && m_dev.numel() ? m_dev.data_ptr<int32_t>() : nullptr;
+  if (wptr)
+    TORCH_CHECK(weights.numel() == order.numel(),
+                "group_pooled_bwd_seg: weights size mismatch");
+  if (r <= 0) r = kSegR;
   if (grad_out.scalar_type() == torch::kBFloat16) {
     auto* gp = reinterpret_cast<const __hip_bfloat16*>(
         grad_out.data_ptr<at::BFloat16>());
-    if (splits <= 1)
-      launch_bwd_strided<__hip_bfloat16, 1>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
-          n_tables, dim, identity_rows, grad_unique, stream);
-    else if (splits <= 8)
-      launch_bwd_strided<__hip_bfloat16, 8>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
-          n_tables, dim, identity_rows, grad_unique, stream);
-    else if (splits <= 16)
-      launch_bwd_strided<__hip_bfloat16, 16, 64>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
-          n_tables, dim, identity_rows, grad_unique, stream);
-    else if (splits <= 32)
-      launch_bwd_strided<__hip_bfloat16, 32, 32>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
+    if (dim >= 16)
+      launch_bwd_seg_r<__hip_bfloat16, 16>(
+          r, gp, order, inverse, row_ids, wptr, row_coeff, m, batch,
           n_tables, dim, identity_rows, grad_unique, stream);
     else
-      launch_bwd_strided<__hip_bfloat16, 64, 16>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
+      launch_bwd_seg_r<__hip_bfloat16, 8>(
+          r, gp, order, inverse, row_ids, wptr, row_coeff, m, batch,
           n_tables, dim, identity_rows, grad_unique, stream);
   } else {
     auto* gp = grad_out.data_ptr<float>();
-    if (splits <= 1)
-      launch_bwd_strided<float, 1>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
+    if (dim >= 16)
+      launch_bwd_seg_r<float, 16>(
+          r, gp, order, inverse, row_ids, wptr, row_coeff, m, batch,
           n_tables, dim, identity_rows, grad_unique, stream);
     else
-      launch_bwd_strided<float, 8>(
-          gp, order, bounds, row_ids, wptr, row_coeff, m, mdp, batch,
+      launch_bwd_seg_r<float, 8>(
+          r, gp, order, inverse, row_ids, wptr, row_coeff, m, batch,
           n_tables, dim, identity_rows, grad_unique, stream);
   }
   return grad_unique;
@@ -1769,7 +1905,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("pooled_bwd", &pooled_bwd);
   mod.def("group_pooled_fwd", &group_pooled_fwd);
   mod.def("group_pooled_fwd_direct", &group_pooled_fwd_direct);
-  mod.def("group_pooled_bwd_strided", &group_pooled_bwd_strided);
+  mod.def("group_pooled_bwd_seg", &group_pooled_bwd_seg);
+  mod.attr("BWD_SEG_R") = (int64_t)kSegR;
   mod.def("apply_sgd", &apply_sgd);
   mod.def("apply_adagrad", &apply_adagrad);
   mod.def("apply_adagrad_decay", &apply_adagrad_decay);

@@ -161,12 +161,11 @@ class ShardedEmbeddingCollection:
             return coll._forward(uniq, None, inverse, offsets_cat,
                                  weights_cat, batch, out_dtype,
                                  emb_override=emb)
-        order, bounds, chunk_u, chunk_k0 = coll._prep_backward(inverse,
-                                                               counts)
+        order, bounds = coll._prep_backward(inverse, counts)
         return _ShardedCollectionLookup.apply(
             coll._anchor, self, uniq, counts, inverse, offsets_cat,
-            row_ids_cat, order, bounds, chunk_u, chunk_k0, row_coeff,
-            weights_cat, batch, out_dtype)
+            row_ids_cat, order, bounds, row_coeff, weights_cat, batch,
+            out_dtype)
 
     # ---- static-shape (padded) exchange — hipGraph-capturable ----
     def static_mode(self, pad_cap: int):
@@ -252,14 +251,14 @@ def _padded_sharded_lookup(sev, values_cat, offsets_cat, row_ids_cat,
         send_keys, send_cnt, route_pos = st.ext.route_pad(
             uniq_buf, counts, m_dev, w, cap, KEY_BITS, st.error_flag)
         # CSR prep consumes pass C's rank before anything else overwrites
-        order, bounds, _, _ = coll._prep_backward(inverse, counts)
+        order, bounds = coll._prep_backward(inverse, counts)
         m_req = values_cat.numel()
     else:
         uniq, inv_t, cnt_t = torch.unique(
             values_cat, return_inverse=True, return_counts=True)
         inverse = inv_t.to(torch.int32)
         st._last_rank = None
-        order, bounds, _, _ = coll._prep_backward(inverse, cnt_t)
+        order, bounds = coll._prep_backward(inverse, cnt_t)
         send_keys, send_cnt, route_pos = _route_pad_cpu(
             uniq, cnt_t, w, cap, KEY_BITS)
         m_dev = None
@@ -304,15 +303,15 @@ def _padded_sharded_lookup(sev, values_cat, offsets_cat, row_ids_cat,
         inverse_final = inverse_final.to(torch.int32)
     return _PaddedShardedLookup.apply(
         coll._anchor, sev, emb_rows, keys_for_kernel, inverse_final,
-        offsets_cat, row_ids_cat, order, bounds, row_coeff, weights_cat,
-        batch, out_dtype, m_req, m_dev, route_pos, inv2, slots2, uniq2,
-        own_valid)
+        offsets_cat, row_ids_cat, order, bounds, inverse, row_coeff,
+        weights_cat, batch, out_dtype, m_req, m_dev, route_pos, inv2, slots2,
+        uniq2, own_valid)
 
 
 class _PaddedShardedLookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, sev, emb_rows, keys_for_kernel, inverse_final,
-                offsets_cat, row_ids_cat, order, bounds, row_coeff,
+                offsets_cat, row_ids_cat, order, bounds, inverse, row_coeff,
                 weights_cat, batch, out_dtype, m_req, m_dev, route_pos,
                 inv2, slots2, uniq2, own_valid):
         out = sev.local._forward(keys_for_kernel, None, inverse_final,
@@ -324,7 +323,7 @@ class _PaddedShardedLookup(torch.autograd.Function):
         ctx.m_req = m_req
         ctx.m_dev = m_dev
         ctx.own_valid = own_valid
-        ctx.save_for_backward(order, bounds, row_ids_cat, row_coeff,
+        ctx.save_for_backward(order, bounds, inverse, row_ids_cat, row_coeff,
                               route_pos, inv2, slots2, uniq2)
         return out
 
@@ -335,9 +334,9 @@ class _PaddedShardedLookup(torch.autograd.Function):
         st = coll.storage
         w, cap = sev.world, sev._pad_cap
         splits = [cap] * w
-        order, bounds, row_ids_cat, row_coeff, route_pos, inv2, slots2, \
-            uniq2 = ctx.saved_tensors
-        grad_unique = coll._backward(grad_out, order, bounds, None, None,
+        order, bounds, inverse, row_ids_cat, row_coeff, route_pos, inv2, \
+            slots2, uniq2 = ctx.saved_tensors
+        grad_unique = coll._backward(grad_out, order, bounds, inverse,
                                      row_ids_cat, ctx.weights_cat,
                                      row_coeff, ctx.m_req, ctx.batch)
         if coll.device.type == "cuda":
@@ -354,7 +353,7 @@ class _PaddedShardedLookup(torch.autograd.Function):
             grad2.index_add_(0, inv2, grad_recv)
             valid = ctx.own_valid
             coll.accumulate_grad(slots2, uniq2[valid], grad2[valid])
-        return (torch.zeros_like(coll._anchor),) + (None,) * 19
+        return (torch.zeros_like(coll._anchor),) + (None,) * 20
 
 
 def _a2a(sev: ShardedEmbeddingCollection, tensor, in_sp, out_sp):
@@ -413,8 +412,8 @@ def _exchange_lookup(sev: ShardedEmbeddingCollection, uniq, counts, train):
 class _ShardedCollectionLookup(torch.autograd.Function):
     @staticmethod
     def forward(ctx, anchor, sev, uniq, counts, inverse, offsets_cat,
-                row_ids_cat, order, bounds, chunk_u, chunk_k0, row_coeff,
-                weights_cat, batch, out_dtype):
+                row_ids_cat, order, bounds, row_coeff, weights_cat, batch,
+                out_dtype):
         emb, ex_ctx = _exchange_lookup(sev, uniq, counts, train=True)
         out = sev.local._forward(uniq, None, inverse, offsets_cat,
                                  weights_cat, batch, out_dtype,
@@ -422,20 +421,20 @@ class _ShardedCollectionLookup(torch.autograd.Function):
         ctx.sev = sev
         ctx.batch = batch
         ctx.weights_cat = weights_cat
-        ctx.chunks = (chunk_u, chunk_k0)
         ctx.ex = ex_ctx
-        ctx.save_for_backward(uniq, order, bounds, row_ids_cat, row_coeff)
+        ctx.save_for_backward(uniq, order, bounds, inverse, row_ids_cat,
+                              row_coeff)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
         sev = ctx.sev
         coll = sev.local
-        uniq, order, bounds, row_ids_cat, row_coeff = ctx.saved_tensors
-        chunk_u, chunk_k0 = ctx.chunks
+        uniq, order, bounds, inverse, row_ids_cat, row_coeff = \
+            ctx.saved_tensors
         order_o, inv2, slots2, uniq2, in_sp, out_sp = ctx.ex
-        grad_unique = coll._backward(grad_out, order, bounds, chunk_u,
-                                     chunk_k0, row_ids_cat, ctx.weights_cat,
+        grad_unique = coll._backward(grad_out, order, bounds, inverse,
+                                     row_ids_cat, ctx.weights_cat,
                                      row_coeff, uniq.numel(), ctx.batch)
         grad_send = grad_unique[order_o]
         grad_recv = _a2a(sev, grad_send.contiguous(), in_sp, out_sp)
@@ -443,4 +442,4 @@ class _ShardedCollectionLookup(torch.autograd.Function):
                             device=grad_recv.device, dtype=grad_recv.dtype)
         grad2.index_add_(0, inv2.long(), grad_recv)
         coll.accumulate_grad(slots2, uniq2, grad2)
-        return (torch.zeros_like(coll._anchor),) + (None,) * 14
+        return (torch.zeros_like(coll._anchor),) + (None,) * 12
