@@ -17,11 +17,13 @@
 // Memory strategy per kernel (all measured on the DLRM layer mix):
 //   fwd: operands straight from L2 (weights are L2-resident, A rows
 //        stream); 64x64 block tiles maximize block count.
-//   dX:  W columns are strided -> LDS-staged transposed W tile for the
-//        wide-N layers (k_linear_dx_lds), direct for narrow ones.
-//   dW:  both operands are column reads -> transposed LDS chunks + multi-
-//        chunk register accumulation to bound the fp32 atomic flush
-//        volume (k_linear_dw_lds64t); 16-col variant for narrow N.
+//   dX:  W columns are strided -> W tile staged row-major in LDS and read
+//        with the transposed LDS read for the wide-N layers
+//        (k_linear_dx_lds), direct for narrow ones.
+//   dW:  both operands are column reads -> row-major LDS chunks read
+//        transposed + multi-chunk register accumulation to bound the fp32
+//        atomic flush volume (k_linear_dw_lds64t); 16-col variant for
+//        narrow N.
 
 #include <torch/extension.h>
 #include <ATen/hip/HIPContext.h>
@@ -107,6 +109,64 @@ __device__ __forceinline__ bf16x8 load_frag_col(const short* __restrict__ src,
     out[i] = v;
   }
   return out;
+}
+
+// ------------------------------------------------------------------
+// Row-major LDS tile for operands that arrive by rows and are consumed by
+// columns (dW's G and A chunks, dX's W superchunk): [rows][64] bf16, 128-B
+// rows, no padding. It is filled with one 16-B store per 16-B global load
+// and read back with gfx950's transposed read ds_read_b64_tr_b16: per 16-
+// lane group the read takes a block of 4 rows x 16 columns, lane 4q+p of
+// the group supplies the address of row q, columns 4p..4p+3, and lane i
+// receives column i, row q in element q. A 16x16x32 MFMA fragment (k slots
+// 8*(lane/16)+i = tile rows r0+8*(lane/16)+i, fragment row/col = tile
+// column cb+lane%16) is two such reads: rows +0..+3 and rows +4..+7.
+//
+// Banks. The transposed read banks by (addr/4) % 64 per 32-lane half. A
+// half holds groups g = 2a and 2a+1, i.e. the 8 tile rows r0+16a+8b+4h+q
+// (b, q vary) x one 32-B column block: 8 spans of 8 dwords, 64 dwords, so
+// it is conflict-free only if the spans tile all 64 banks. With 128-B rows
+// the row contributes 32*(row&1) dwords; the 32-B column block cb/16 is
+// XORed with sw(row) = bit1(row) | bit3(row)<<1 = (q>>1) | b<<1, so the
+// span starts at 32*(q&1) + 8*((cb/16) ^ sw): all eight (q&1, sw) pairs
+// differ -> conflict-free. (Unswizzled padded rows cannot do it: any
+// stride that is a multiple of 32 B puts rows r and r+8 on the same
+// banks, and a 144-B stride is 2-way.) Stores bank by (addr/4) % 32 in
+// groups of 8 consecutive lanes, which here are the eight 16-B segments
+// of one row: a permutation of 128 contiguous bytes, conflict-free.
+//
+// Rules of the transposed read: every lane's address 8-byte aligned and
+// inside the tile, and EXEC all ones — the gather crosses lanes, so it
+// must stay outside lane-divergent control flow (wave-uniform branches
+// are fine); ragged edges are zero-padded in the tile, never masked.
+// ------------------------------------------------------------------
+using bf16x4 = __attribute__((ext_vector_type(4))) short;
+constexpr int TRT_COLS = 64;
+
+// element offset of tile[row][col..]; col % 4 == 0 (and % 8 == 0 for the
+// 16-B stores), the 4 (8) elements stay inside one 32-B column block
+__device__ __forceinline__ int trt_off(int row, int col) {
+  const int sw = ((row >> 1) & 1) | ((row >> 2) & 2);
+  return row * TRT_COLS + ((((col >> 4) ^ sw) << 4) | (col & 15));
+}
+
+// this lane's read offset for the fragment of rows r0.., columns cb..cb+15,
+// relative to row r0; r0 % 16 == 0 keeps sw(r0 + row) == sw(row)
+__device__ __forceinline__ int trt_lane_off(int lane, int cb) {
+  return trt_off(8 * (lane >> 4) + ((lane >> 2) & 3), cb + 4 * (lane & 3));
+}
+
+__device__ __forceinline__ bf16x4 lds_read_tr16(const short* p) {
+  return __builtin_amdgcn_ds_read_tr16_b64_v4i16(
+      (__attribute__((address_space(3))) bf16x4*)p);
+}
+
+// fragment whose first read is at p (tile + r0 * TRT_COLS + trt_lane_off):
+// elements 0..3 from rows +0..+3, 4..7 from rows +4..+7 (same sw: bit 2)
+__device__ __forceinline__ bf16x8 trt_frag(const short* p) {
+  const bf16x4 lo = lds_read_tr16(p);
+  const bf16x4 hi = lds_read_tr16(p + 4 * TRT_COLS);
+  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
 // ------------------------------------------------------------------
@@ -259,20 +319,27 @@ __global__ void k_linear_dx(const short* __restrict__ G,
 // dX via LDS-staged weights: the 64-col variant above builds its B
 // fragments from 8 strided global loads each (W columns); for wide N
 // that dominates (measured 37.5us on the 8192x512x480 layer). Here
-// W[:, c0:c0+64] is staged TRANSPOSED into LDS once per 256-row N
-// superchunk (row stride 264 shorts keeps the 16B fragment reads
-// aligned), and each wave computes 32 rows x 64 cols (8 MFMAs per pair
-// of G fragments).
+// W[ns..ns+256][c0..c0+64] is staged ROW-MAJOR into an LDS tile (layout
+// and bank arithmetic: trt_off above) once per 256-row N superchunk, one
+// 16-B store per 16-B global load, and each B fragment (column c, 8
+// consecutive n) is two transposed reads. Each wave computes 32 rows x
+// 64 cols (8 MFMAs per pair of G fragments).
 // ------------------------------------------------------------------
-constexpr int DX_NSUP = 256;  // N rows staged per superchunk (33 KB LDS)
+constexpr int DX_NSUP = 256;  // N rows staged per superchunk (32 KB LDS)
+// 32-row slabs loaded together before their LDS stores: one slab at a time
+// is one L2 round trip per slab; 2 measured 8 % faster per call, 4 another
+// 3 % but 88 VGPRs (5 waves) instead of 72 (7 waves)
+constexpr int DX_STAGE_BATCH = 2;
 __global__ void k_linear_dx_lds(const short* __restrict__ G,
                                 const short* __restrict__ W, int M, int N,
                                 int K, short* __restrict__ dX,
                                 const short* __restrict__ prev_out,
                                 int prev_act) {
-  __shared__ short wl[64][DX_NSUP + 8];
+  __shared__ __attribute__((aligned(16))) short wl[DX_NSUP * TRT_COLS];
   const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
+  // wave-uniform by construction; say so, so that the m0 >= M skip below
+  // is a scalar branch around the transposed reads
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int ktiles64 = (K + 63) / 64;
   const int m0 = (blockIdx.x / ktiles64) * 128 + wave * 32;
   const int c0 = (blockIdx.x % ktiles64) * 64;
@@ -280,21 +347,33 @@ __global__ void k_linear_dx_lds(const short* __restrict__ G,
   const int row_g1 = m0 + 16 + (lane & 15);
   const int kgrp = (lane >> 4) * 8;
   const int kt = min(4, (K - c0 + 15) / 16);
+  // staging: thread -> row tid/8 of each 32-row slab, 16-B segment tid%8
+  const int st_r = threadIdx.x >> 3;
+  const int st_seg = threadIdx.x & 7;
+  const int st_off = trt_off(st_r, st_seg * 8);
+  int b_off[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) b_off[t] = trt_lane_off(lane, t * 16);
   f32x4 acc[2][4] = {};
   for (int ns = 0; ns < N; ns += DX_NSUP) {
     const int nlen = min(DX_NSUP, N - ns);
     __syncthreads();  // previous superchunk's reads must finish
     {
-      // stage W[ns..ns+nlen][c0..c0+64] -> wl[c][n]; rows past N are
-      // zero-filled by load_frag_row so fragment tails read zeros
-      const int r = threadIdx.x >> 3;
-      const int seg = threadIdx.x & 7;
+      // stage W[ns..ns+nlen][c0..c0+64] -> wl[n][c]; rows past N and
+      // columns past K are zero-filled by load_frag_row (no memory access),
+      // and every row a fragment can touch (up to the next multiple of 32)
+      // is rewritten; a batch may run one slab past that, still inside wl
       const int nstg = (nlen + 31) & ~31;
-      for (int it = 0; it * 32 < nstg; ++it) {
-        int n = it * 32 + r;
-        bf16x8 v = load_frag_row(W, ns + n, c0 + seg * 8, N, K);
+      for (int it0 = 0; it0 * 32 < nstg; it0 += DX_STAGE_BATCH) {
+        bf16x8 v[DX_STAGE_BATCH];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) wl[seg * 8 + j][n] = v[j];
+        for (int j = 0; j < DX_STAGE_BATCH; ++j)
+          v[j] = load_frag_row(W, ns + (it0 + j) * 32 + st_r,
+                               c0 + st_seg * 8, N, K);
+#pragma unroll
+        for (int j = 0; j < DX_STAGE_BATCH; ++j)
+          *reinterpret_cast<bf16x8*>(
+              &wl[(it0 + j) * 32 * TRT_COLS + st_off]) = v[j];
       }
     }
     __syncthreads();
@@ -305,8 +384,7 @@ __global__ void k_linear_dx_lds(const short* __restrict__ G,
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         if (t >= kt) break;
-        bf16x8 b = *reinterpret_cast<const bf16x8*>(
-            &wl[t * 16 + (lane & 15)][n0 + kgrp]);
+        bf16x8 b = trt_frag(&wl[n0 * TRT_COLS + b_off[t]]);
         acc[0][t] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0, b, acc[0][t], 0, 0,
                                                     0);
@@ -507,21 +585,29 @@ __global__ void k_linear_dw_lds64(const short* __restrict__ G,
   }
 }
 
-// Transposed-LDS dW: same 64n x 64k tile as lds64, but (a) A and G
-// chunks are stored TRANSPOSED ([col][row], row stride 136 shorts keeps
-// 16B alignment) so each MFMA fragment is ONE aligned b128 LDS read, and
+// Multi-chunk dW: same 64n x 64k tile as lds64, but (a) each MFMA
+// fragment comes from two transposed LDS reads of row-major G and A
+// chunks (layout and bank arithmetic: trt_off above; the chunks are
+// stored as they are loaded, one 16-B store per 16-B global load), and
 // (b) each block accumulates `cpb` consecutive 128-row M chunks in
 // registers before its single atomic flush. The per-chunk atomic flush
 // was the real bound: 64 chunks x N*K fp32 atomics = 63 MB of atomic
 // writes on the 8192x512x480 layer (~31 us of the 60 us).
+// All 128 rows of both tiles are rewritten every chunk (zero-filled past
+// M, N and K by load_frag_row), so a ragged chunk never sums a stale row
+// of the chunk before it.
+// (Issuing the next chunk's global loads before the MFMA loop and storing
+// them after it measured no faster — the 8 loads of a chunk are already in
+// flight together and the CU's other blocks cover them — at 122 VGPRs
+// instead of 70; profiles/PERF_LOG.md.)
 __global__ void k_linear_dw_lds64t(const short* __restrict__ G,
                                    const short* __restrict__ A, int M, int N,
                                    int K, int cpb,
                                    float* __restrict__ dW,
                                    float* __restrict__ dbias) {
   constexpr int CH = 128;
-  __shared__ short a_t[64][CH + 8];
-  __shared__ short g_t[64][CH + 8];
+  __shared__ __attribute__((aligned(16))) short a_s[CH * TRT_COLS];
+  __shared__ __attribute__((aligned(16))) short g_s[CH * TRT_COLS];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
   const int tid = threadIdx.x;
@@ -531,8 +617,13 @@ __global__ void k_linear_dw_lds64t(const short* __restrict__ G,
   const int chunk0 = (blockIdx.x / (ngroups * kgroups)) * cpb;
   const int n0 = (tile_id / kgroups) * 64;
   const int k0 = (tile_id % kgroups) * 64;
-  const int col_g = wave * 16 + (lane & 15);
-  const int kgrp = (lane >> 4) * 8;
+  // staging: thread -> row tid/8 of each 32-row slab, 16-B segment tid%8
+  const int st_r = tid >> 3, st_seg = tid & 7;
+  const int st_off = trt_off(st_r, st_seg * 8);
+  const int g_off = trt_lane_off(lane, wave * 16);
+  int a_off[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) a_off[t] = trt_lane_off(lane, t * 16);
   f32x4 acc[4] = {};
   float bsum = 0.0f;
   const bool do_bias = (dbias != nullptr) && (k0 == 0);
@@ -540,33 +631,30 @@ __global__ void k_linear_dw_lds64t(const short* __restrict__ G,
     const int mbeg = (chunk0 + c) * CH;
     if (mbeg >= M) break;
     if (c > 0) __syncthreads();  // previous chunk's reads must finish
-    {
-      // coalesced global row loads, transposing scalar stores into LDS
-      const int r = tid >> 3, seg = tid & 7;
-      for (int it = 0; it < CH / 32; ++it) {
-        int rr = it * 32 + r;
-        bf16x8 va = load_frag_row(A, mbeg + rr, k0 + seg * 8, M, K);
-        bf16x8 vg = load_frag_row(G, mbeg + rr, n0 + seg * 8, M, N);
+    // coalesced global row loads, all issued before the first LDS store
+    bf16x8 va[CH / 32], vg[CH / 32];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          a_t[seg * 8 + j][rr] = va[j];
-          g_t[seg * 8 + j][rr] = vg[j];
-        }
-      }
+    for (int it = 0; it < CH / 32; ++it) {
+      const int m = mbeg + it * 32 + st_r;
+      va[it] = load_frag_row(A, m, k0 + st_seg * 8, M, K);
+      vg[it] = load_frag_row(G, m, n0 + st_seg * 8, M, N);
+    }
+#pragma unroll
+    for (int it = 0; it < CH / 32; ++it) {
+      *reinterpret_cast<bf16x8*>(&a_s[it * 32 * TRT_COLS + st_off]) = va[it];
+      *reinterpret_cast<bf16x8*>(&g_s[it * 32 * TRT_COLS + st_off]) = vg[it];
     }
     __syncthreads();
 #pragma unroll
     for (int ms = 0; ms < CH; ms += 32) {
-      bf16x8 gfrag =
-          *reinterpret_cast<const bf16x8*>(&g_t[col_g][ms + kgrp]);
+      bf16x8 gfrag = trt_frag(&g_s[ms * TRT_COLS + g_off]);
       if (do_bias) {
 #pragma unroll
         for (int i = 0; i < 8; ++i) bsum += bf2f_u16(gfrag[i]);
       }
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
-        bf16x8 afrag = *reinterpret_cast<const bf16x8*>(
-            &a_t[t * 16 + (lane & 15)][ms + kgrp]);
+        bf16x8 afrag = trt_frag(&a_s[ms * TRT_COLS + a_off[t]]);
         acc[t] =
             __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfrag, afrag, acc[t],
                                                     0, 0, 0);
