@@ -45,9 +45,17 @@ def _so_path() -> str:
     return os.path.join(_EXT_DIR, f"{_EXT_NAME}.so")
 
 
+def _headers():
+    hip_dir = os.path.join(_HERE, "hip")
+    return sorted(os.path.join(hip_dir, f) for f in os.listdir(hip_dir)
+                  if f.endswith((".h", ".hpp")))
+
+
 def _sources_digest() -> str:
+    """Digest of everything a rebuild depends on: sources and the headers
+    next to them."""
     h = hashlib.sha256()
-    for s in _SOURCES:
+    for s in _SOURCES + _headers():
         with open(s, "rb") as f:
             h.update(f.read())
     return h.hexdigest()[:16]

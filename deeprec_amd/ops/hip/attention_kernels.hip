@@ -15,29 +15,9 @@
 // (modelzoo/bst/train.py, modelzoo/din/train.py:207-253 attention); the
 // kernel design is new for this engine.
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-
-#include <cstdint>
+#include "hip_common.h"
 
 namespace {
-
-static inline hipStream_t att_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
-
-__device__ __forceinline__ float bfu(short u) {
-  unsigned int x = ((unsigned int)(unsigned short)u) << 16;
-  return __uint_as_float(x);
-}
-__device__ __forceinline__ short fbu(float f) {
-  // round-to-nearest-even bf16
-  unsigned int x = __float_as_uint(f);
-  unsigned int r = x + 0x7FFF + ((x >> 16) & 1);
-  return (short)(r >> 16);
-}
 
 constexpr int kMaxDh = 32;  // head dim cap (template dispatch below)
 
@@ -73,14 +53,14 @@ __global__ void k_mha_fwd(const short* __restrict__ q,
     float qv[DH];
     const short* qp = q + base + (int64_t)qr * D + h * dh;
 #pragma unroll
-    for (int d = 0; d < dh; ++d) qv[d] = bfu(qp[d]);
+    for (int d = 0; d < dh; ++d) qv[d] = bf2f_u16(qp[d]);
     // pass 1: row max
     float mx = -1e30f;
     for (int t = 0; t < T; ++t) {
       if (pad[t]) continue;
       const short* kp = K + t * D + h * dh;
       float s = 0.0f;
-      for (int d = 0; d < dh; ++d) s += qv[d] * bfu(kp[d]);
+      for (int d = 0; d < dh; ++d) s += qv[d] * bf2f_u16(kp[d]);
       s *= scale;
       mx = fmaxf(mx, s);
     }
@@ -93,15 +73,15 @@ __global__ void k_mha_fwd(const short* __restrict__ q,
       if (pad[t]) continue;
       const short* kp = K + t * D + h * dh;
       float s = 0.0f;
-      for (int d = 0; d < dh; ++d) s += qv[d] * bfu(kp[d]);
+      for (int d = 0; d < dh; ++d) s += qv[d] * bf2f_u16(kp[d]);
       float p = __expf(s * scale - mx);
       sum += p;
       const short* vp = V + t * D + h * dh;
-      for (int d = 0; d < dh; ++d) acc[d] += p * bfu(vp[d]);
+      for (int d = 0; d < dh; ++d) acc[d] += p * bf2f_u16(vp[d]);
     }
     const float inv = 1.0f / fmaxf(sum, 1e-20f);
     short* op = out + base + (int64_t)qr * D + h * dh;
-    for (int d = 0; d < dh; ++d) op[d] = fbu(acc[d] * inv);
+    for (int d = 0; d < dh; ++d) op[d] = f2bf_u16(acc[d] * inv);
     float* st = stats + (((int64_t)b * H + h) * T + qr) * 2;
     st[0] = mx;
     st[1] = sum;
@@ -149,8 +129,8 @@ __global__ void k_mha_bwd(const short* __restrict__ dout,
     float qv[DH], go[DH];
 #pragma unroll
     for (int d = 0; d < dh; ++d) {
-      qv[d] = bfu(Q[qr * D + h * dh + d]);
-      go[d] = bfu(dO[qr * D + h * dh + d]);
+      qv[d] = bf2f_u16(Q[qr * D + h * dh + d]);
+      go[d] = bf2f_u16(dO[qr * D + h * dh + d]);
     }
     float rd = 0.0f;
     for (int t = 0; t < T; ++t) {
@@ -159,8 +139,8 @@ __global__ void k_mha_bwd(const short* __restrict__ dout,
       const short* kp = K + t * D + h * dh;
       const short* vp = V + t * D + h * dh;
       for (int d = 0; d < dh; ++d) {
-        s += qv[d] * bfu(kp[d]);
-        dp += go[d] * bfu(vp[d]);
+        s += qv[d] * bf2f_u16(kp[d]);
+        dp += go[d] * bf2f_u16(vp[d]);
       }
       rd += __expf(s * scale - mx) * inv * dp;
     }
@@ -174,15 +154,15 @@ __global__ void k_mha_bwd(const short* __restrict__ dout,
       const short* kp = K + t * D + h * dh;
       const short* vp = V + t * D + h * dh;
       for (int d = 0; d < dh; ++d) {
-        s += qv[d] * bfu(kp[d]);
-        dp += go[d] * bfu(vp[d]);
+        s += qv[d] * bf2f_u16(kp[d]);
+        dp += go[d] * bf2f_u16(vp[d]);
       }
       float p = __expf(s * scale - mx) * inv;
       float ds = p * (dp - rd) * scale;
-      for (int d = 0; d < dh; ++d) dqv[d] += ds * bfu(kp[d]);
+      for (int d = 0; d < dh; ++d) dqv[d] += ds * bf2f_u16(kp[d]);
     }
     short* dqp = dq + base + (int64_t)qr * D + h * dh;
-    for (int d = 0; d < dh; ++d) dqp[d] = fbu(dqv[d]);
+    for (int d = 0; d < dh; ++d) dqp[d] = f2bf_u16(dqv[d]);
   }
   __syncthreads();
   // phase B: per (key row, head): dK, dV
@@ -201,8 +181,8 @@ __global__ void k_mha_bwd(const short* __restrict__ dout,
     float kv[DH], vv[DH], dkv[DH], dvv[DH];
 #pragma unroll
     for (int d = 0; d < dh; ++d) {
-      kv[d] = bfu(K[t * D + h * dh + d]);
-      vv[d] = bfu(V[t * D + h * dh + d]);
+      kv[d] = bf2f_u16(K[t * D + h * dh + d]);
+      vv[d] = bf2f_u16(V[t * D + h * dh + d]);
       dkv[d] = 0.0f;
       dvv[d] = 0.0f;
     }
@@ -214,19 +194,19 @@ __global__ void k_mha_bwd(const short* __restrict__ dout,
       const short* qp = Q + qr * D + h * dh;
       const short* gp = dO + qr * D + h * dh;
       for (int d = 0; d < dh; ++d) {
-        s += bfu(qp[d]) * kv[d];
-        dp += bfu(gp[d]) * vv[d];
+        s += bf2f_u16(qp[d]) * kv[d];
+        dp += bf2f_u16(gp[d]) * vv[d];
       }
       float p = __expf(s * scale - mx) * inv;
       float ds = p * (dp - row_dot[qr * H + h]) * scale;
       for (int d = 0; d < dh; ++d) {
-        dkv[d] += ds * bfu(qp[d]);
-        dvv[d] += p * bfu(gp[d]);
+        dkv[d] += ds * bf2f_u16(qp[d]);
+        dvv[d] += p * bf2f_u16(gp[d]);
       }
     }
     for (int d = 0; d < dh; ++d) {
-      dkp[d] = fbu(dkv[d]);
-      dvp[d] = fbu(dvv[d]);
+      dkp[d] = f2bf_u16(dkv[d]);
+      dvp[d] = f2bf_u16(dvv[d]);
     }
   }
 }
@@ -249,10 +229,10 @@ __global__ void k_din_feat_fwd(const float* __restrict__ seq,
     float s = seq[i];
     float t = tgt[(int64_t)b * D + d];
     short* o = out + bt * 4 * D + d;
-    o[0] = fbu(s);
-    o[D] = fbu(t);
-    o[2 * D] = fbu(s - t);
-    o[3 * D] = fbu(s * t);
+    o[0] = f2bf_u16(s);
+    o[D] = f2bf_u16(t);
+    o[2 * D] = f2bf_u16(s - t);
+    o[3 * D] = f2bf_u16(s * t);
   }
 }
 
@@ -272,8 +252,8 @@ __global__ void k_din_feat_bwd_ds(const short* __restrict__ g,
     int64_t bt = i / D;
     int b = (int)(bt / T);
     const short* gp = g + bt * 4 * D + d;
-    dseq[i] = bfu(gp[0]) + bfu(gp[2 * D])
-              + bfu(gp[3 * D]) * tgt[(int64_t)b * D + d];
+    dseq[i] = bf2f_u16(gp[0]) + bf2f_u16(gp[2 * D])
+              + bf2f_u16(gp[3 * D]) * tgt[(int64_t)b * D + d];
   }
 }
 
@@ -291,8 +271,8 @@ __global__ void k_din_feat_bwd_dt(const short* __restrict__ g,
     for (int t = 0; t < T; ++t) {
       int64_t bt = (int64_t)b * T + t;
       const short* gp = g + bt * 4 * D + d;
-      acc += bfu(gp[D]) - bfu(gp[2 * D])
-             + bfu(gp[3 * D]) * seq[bt * D + d];
+      acc += bf2f_u16(gp[D]) - bf2f_u16(gp[2 * D])
+             + bf2f_u16(gp[3 * D]) * seq[bt * D + d];
     }
     dtgt[i] = acc;
   }
@@ -434,7 +414,7 @@ std::tuple<torch::Tensor, torch::Tensor> mha_fwd(torch::Tensor q,
   TORCH_CHECK(dh == 4 || dh == 8 || dh == 16 || dh == 32,
               "head dim must be 4/8/16/32");
 #define MHA_FWD(DHV) \
-  k_mha_fwd<DHV><<<B, threads, lds, att_stream()>>>( \
+  k_mha_fwd<DHV><<<B, threads, lds, current_hip_stream()>>>( \
       att_bf_ptr(q), att_bf_ptr(k), att_bf_ptr(v), \
       key_pad.data_ptr<uint8_t>(), B, T, D, H, (float)scale, \
       att_bf_ptr_mut(out), stats.data_ptr<float>())
@@ -461,7 +441,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> mha_bwd(
   int threads = std::min(1024, ((T * H + 63) / 64) * 64);
   const int dh = D / H;
 #define MHA_BWD(DHV) \
-  k_mha_bwd<DHV><<<B, threads, lds, att_stream()>>>( \
+  k_mha_bwd<DHV><<<B, threads, lds, current_hip_stream()>>>( \
       att_bf_ptr(dout.contiguous()), att_bf_ptr(q), att_bf_ptr(k), \
       att_bf_ptr(v), key_pad.data_ptr<uint8_t>(), stats.data_ptr<float>(), \
       B, T, D, H, (float)scale, att_bf_ptr_mut(dq), att_bf_ptr_mut(dk), \
@@ -481,7 +461,7 @@ torch::Tensor din_feat_fwd(torch::Tensor seq, torch::Tensor tgt) {
                           seq.options().dtype(torch::kBFloat16));
   int64_t total = (int64_t)B * T * D;
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
-  k_din_feat_fwd<<<blocks, 256, 0, att_stream()>>>(
+  k_din_feat_fwd<<<blocks, 256, 0, current_hip_stream()>>>(
       seq.data_ptr<float>(), tgt.data_ptr<float>(), B, T, D,
       att_bf_ptr_mut(out));
   return out;
@@ -496,11 +476,11 @@ std::tuple<torch::Tensor, torch::Tensor> din_feat_bwd(torch::Tensor g,
   auto gc = g.contiguous();
   int64_t total = (int64_t)B * T * D;
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
-  k_din_feat_bwd_ds<<<blocks, 256, 0, att_stream()>>>(
+  k_din_feat_bwd_ds<<<blocks, 256, 0, current_hip_stream()>>>(
       att_bf_ptr(gc), tgt.data_ptr<float>(), B, T, D,
       dseq.data_ptr<float>());
   int blocks2 = (int)std::min<int64_t>(((int64_t)B * D + 255) / 256, 8192);
-  k_din_feat_bwd_dt<<<blocks2, 256, 0, att_stream()>>>(
+  k_din_feat_bwd_dt<<<blocks2, 256, 0, current_hip_stream()>>>(
       att_bf_ptr(gc), seq.data_ptr<float>(), B, T, D,
       dtgt.data_ptr<float>());
   return {dseq, dtgt};
@@ -519,7 +499,7 @@ std::tuple<torch::Tensor, torch::Tensor> msm_pool_fwd(torch::Tensor scores,
   auto w = torch::empty_like(scores);
   auto out = torch::empty({(int64_t)B, (int64_t)D}, seq.options());
   if (B == 0) return {out, w};
-  k_msm_pool_fwd<<<B, 128, (size_t)T * sizeof(float), att_stream()>>>(
+  k_msm_pool_fwd<<<B, 128, (size_t)T * sizeof(float), current_hip_stream()>>>(
       scores.data_ptr<float>(), seq.data_ptr<float>(),
       mask.data_ptr<uint8_t>(), B, T, D, w.data_ptr<float>(),
       out.data_ptr<float>());
@@ -535,7 +515,8 @@ std::tuple<torch::Tensor, torch::Tensor> msm_pool_bwd(torch::Tensor dout,
   auto dscores = torch::empty_like(w);
   auto dseq = torch::empty_like(seq);
   if (B == 0) return {dscores, dseq};
-  k_msm_pool_bwd<<<B, 128, (size_t)(T + D) * sizeof(float), att_stream()>>>(
+  k_msm_pool_bwd<<<B, 128, (size_t)(T + D) * sizeof(float),
+                   current_hip_stream()>>>(
       dc.data_ptr<float>(), seq.data_ptr<float>(), w.data_ptr<float>(),
       mask.data_ptr<uint8_t>(), B, T, D, dscores.data_ptr<float>(),
       dseq.data_ptr<float>());

@@ -20,51 +20,23 @@
 //   dX:  W columns are strided -> W tile staged row-major in LDS and read
 //        with the transposed LDS read for the wide-N layers
 //        (k_linear_dx_lds), direct for narrow ones.
-//   dW:  both operands are column reads -> row-major LDS chunks read
-//        transposed + multi-chunk register accumulation to bound the fp32
-//        atomic flush volume (k_linear_dw_lds64t); 16-col variant for
-//        narrow N.
+//   dW:  both operands are column reads -> LDS chunks. N >= 64: 64n x 64k
+//        tiles staged row-major and read transposed, several M chunks
+//        accumulated in registers to bound the fp32 atomic flush volume
+//        (k_linear_dw_lds64t). Narrow N: 16n x 64k tiles, padded LDS rows
+//        and scalar column reads (k_linear_dw_lds).
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "hip_common.h"
 
 #include <algorithm>
-#include <cstdint>
 
 namespace py = pybind11;
-
-static inline hipStream_t dense_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
 
 namespace {
 
 using bf16 = __hip_bfloat16;
 using bf16x8 = __attribute__((ext_vector_type(8))) short;
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ float bf2f_u16(short u) {
-  union {
-    unsigned int i;
-    float f;
-  } cv;
-  cv.i = ((unsigned int)(unsigned short)u) << 16;
-  return cv.f;
-}
-
-__device__ __forceinline__ short f2bf_u16(float f) {
-  union {
-    float f;
-    unsigned int i;
-  } cv;
-  cv.f = f;
-  // round-to-nearest-even
-  unsigned int lsb = (cv.i >> 16) & 1;
-  cv.i += 0x7fff + lsb;
-  return (short)(cv.i >> 16);
-}
 
 // activation gradient of one element: g * act'(out), with out the saved
 // bf16 activation; act 1=relu, 2=sigmoid. Shared by k_act_bwd and the dX
@@ -169,6 +141,107 @@ __device__ __forceinline__ bf16x8 trt_frag(const short* p) {
   return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
 }
 
+// Filling such a tile with a 256-thread block, 32 rows (a slab) at a time:
+// thread -> row tid/8 of each slab, 16-B segment tid%8. The kernels keep
+// their own load batching: load() several slabs, then store() them. A
+// kernel that uses it is launched with exactly TRT_STAGE_THREADS threads;
+// with fewer, slab rows stay unwritten, with more, stores leave the slab.
+constexpr int TRT_STAGE_THREADS = 256;
+static_assert(TRT_STAGE_THREADS / 8 == 32, "a slab is 32 rows of 8 segments");
+struct TrtStager {
+  int row, col, off;  // row in the slab, first column, swizzled offset
+  __device__ __forceinline__ explicit TrtStager(int tid)
+      : row(tid >> 3), col((tid & 7) * 8), off(trt_off(row, col)) {}
+  // this thread's 16 B of src[row0 + 32 slab ..][col0 ..], zero-filled
+  // outside [rows, cols]
+  __device__ __forceinline__ bf16x8 load(const short* __restrict__ src,
+                                         int row0, int slab, int col0,
+                                         int rows, int cols) const {
+    return load_frag_row(src, row0 + slab * 32 + row, col0 + col, rows, cols);
+  }
+  __device__ __forceinline__ void store(short* tile, int slab,
+                                        bf16x8 v) const {
+    *reinterpret_cast<bf16x8*>(&tile[slab * 32 * TRT_COLS + off]) = v;
+  }
+};
+
+// ------------------------------------------------------------------
+// Epilogue pieces. They hold per-lane bounds checks, so none of them may
+// contain a transposed read.
+// ------------------------------------------------------------------
+
+// one forward element: act(acc + bias) rounded to bf16; act 1=relu (written
+// as v < 0 -> 0 so that NaN passes through), 2=sigmoid
+__device__ __forceinline__ short fwd_act_u16(float acc, float bv, int act) {
+  float v = acc + bv;
+  if (act == 1 && v < 0.0f) v = 0.0f;
+  else if (act == 2) v = 1.0f / (1.0f + __expf(-v));
+  return f2bf_u16(v);
+}
+
+// dX store of one wave's 16 x 64 accumulator tile at (m0, c0), kt live
+// 16-column subtiles: round to bf16, then (prev_out set) the activation
+// gradient of the layer below; bounded by M and K.
+__device__ __forceinline__ void dx_store_tile(
+    const f32x4 (&acc)[4], int lane, int m0, int c0, int kt, int M, int K,
+    short* __restrict__ dX, const short* __restrict__ prev_out,
+    int prev_act) {
+#pragma unroll
+  for (int t = 0; t < 4; ++t) {
+    if (t >= kt) break;
+    const int ck = c0 + t * 16 + (lane & 15);
+    if (ck >= K) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int cm = m0 + (lane >> 4) * 4 + i;
+      if (cm >= M) continue;
+      short v = f2bf_u16(acc[t][i]);
+      if (prev_out)
+        v = act_grad_u16(v, prev_out[(int64_t)cm * K + ck], prev_act);
+      dX[(int64_t)cm * K + ck] = v;
+    }
+  }
+}
+
+// dW flush of one wave's NT 16 x 16 accumulators, rows n0.., columns
+// k0 + 16 t..: fp32 atomic accumulate, bounded by N and K.
+template <int NT>
+__device__ __forceinline__ void dw_flush(const f32x4 (&acc)[NT], int lane,
+                                         int n0, int k0, int N, int K,
+                                         float* __restrict__ dW) {
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    const int ck = k0 + t * 16 + (lane & 15);
+    if (ck >= K) continue;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int cn = n0 + (lane >> 4) * 4 + i;
+      if (cn >= N) continue;
+      atomicAdd(&dW[(int64_t)cn * K + ck], acc[t][i]);
+    }
+  }
+}
+
+// dbias: each lane sums its 8 m slots of column n0 + lane%16 of every G
+// fragment (in slot order) ...
+__device__ __forceinline__ float dbias_add_frag(float bsum, bf16x8 gfrag) {
+#pragma unroll
+  for (int i = 0; i < 8; ++i) bsum += bf2f_u16(gfrag[i]);
+  return bsum;
+}
+
+// ... and at the end the four lanes of a column are reduced within the
+// wave, one atomic per column. Call it wave-uniformly.
+__device__ __forceinline__ void dbias_reduce_add(float bsum, int lane, int n0,
+                                                 int N,
+                                                 float* __restrict__ dbias) {
+  float v = bsum;
+  for (int off = 16; off < 64; off += 16)
+    v += __shfl(bsum, (lane & 15) + off);
+  const int cn = n0 + (lane & 15);
+  if (lane < 16 && cn < N) atomicAdd(&dbias[cn], v);
+}
+
 // ------------------------------------------------------------------
 // fwd: C[M,N] = act(A[M,K] @ W[N,K]^T + bias); 4 waves/block stacked on M.
 // MT = m-subtiles per wave: each wave computes MT*16 rows x 64 cols, so
@@ -222,10 +295,8 @@ __global__ void k_linear_fwd_t(const short* __restrict__ A,
       const float bv = bias ? bias[n0 + cn] : 0.0f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float v = acc[0][t][i] + bv;
-        if (act == 1 && v < 0.0f) v = 0.0f;
-        else if (act == 2) v = 1.0f / (1.0f + __expf(-v));
-        cstage[wave][(lane >> 4) * 4 + i][cn] = f2bf_u16(v);
+        cstage[wave][(lane >> 4) * 4 + i][cn] =
+            fwd_act_u16(acc[0][t][i], bv, act);
       }
     }
     __builtin_amdgcn_s_waitcnt(0);  // LDS writes visible within the wave
@@ -255,10 +326,7 @@ __global__ void k_linear_fwd_t(const short* __restrict__ A,
       for (int i = 0; i < 4; ++i) {
         int cm = m0 + r * 16 + (lane >> 4) * 4 + i;
         if (cm >= M) continue;
-        float v = acc[r][t][i] + bv;
-        if (act == 1 && v < 0.0f) v = 0.0f;          // relu
-        else if (act == 2) v = 1.0f / (1.0f + __expf(-v));  // sigmoid
-        C[(int64_t)cm * N + cn] = f2bf_u16(v);
+        C[(int64_t)cm * N + cn] = fwd_act_u16(acc[r][t][i], bv, act);
       }
     }
   }
@@ -298,21 +366,7 @@ __global__ void k_linear_dx(const short* __restrict__ G,
                                                        0);
     }
   }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    if (t >= kt) break;
-    const int ck = c0 + t * 16 + (lane & 15);
-    if (ck >= K) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int cm = m0 + (lane >> 4) * 4 + i;
-      if (cm >= M) continue;
-      short v = f2bf_u16(acc[t][i]);
-      if (prev_out)
-        v = act_grad_u16(v, prev_out[(int64_t)cm * K + ck], prev_act);
-      dX[(int64_t)cm * K + ck] = v;
-    }
-  }
+  dx_store_tile(acc, lane, m0, c0, kt, M, K, dX, prev_out, prev_act);
 }
 
 // ------------------------------------------------------------------
@@ -347,10 +401,7 @@ __global__ void k_linear_dx_lds(const short* __restrict__ G,
   const int row_g1 = m0 + 16 + (lane & 15);
   const int kgrp = (lane >> 4) * 8;
   const int kt = min(4, (K - c0 + 15) / 16);
-  // staging: thread -> row tid/8 of each 32-row slab, 16-B segment tid%8
-  const int st_r = threadIdx.x >> 3;
-  const int st_seg = threadIdx.x & 7;
-  const int st_off = trt_off(st_r, st_seg * 8);
+  const TrtStager stg(threadIdx.x);
   int b_off[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) b_off[t] = trt_lane_off(lane, t * 16);
@@ -368,12 +419,9 @@ __global__ void k_linear_dx_lds(const short* __restrict__ G,
         bf16x8 v[DX_STAGE_BATCH];
 #pragma unroll
         for (int j = 0; j < DX_STAGE_BATCH; ++j)
-          v[j] = load_frag_row(W, ns + (it0 + j) * 32 + st_r,
-                               c0 + st_seg * 8, N, K);
+          v[j] = stg.load(W, ns, it0 + j, c0, N, K);
 #pragma unroll
-        for (int j = 0; j < DX_STAGE_BATCH; ++j)
-          *reinterpret_cast<bf16x8*>(
-              &wl[(it0 + j) * 32 * TRT_COLS + st_off]) = v[j];
+        for (int j = 0; j < DX_STAGE_BATCH; ++j) stg.store(wl, it0 + j, v[j]);
       }
     }
     __syncthreads();
@@ -396,31 +444,16 @@ __global__ void k_linear_dx_lds(const short* __restrict__ G,
   }
   if (m0 >= M) return;
 #pragma unroll
-  for (int rg = 0; rg < 2; ++rg) {
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      if (t >= kt) break;
-      const int ck = c0 + t * 16 + (lane & 15);
-      if (ck >= K) continue;
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        int cm = m0 + rg * 16 + (lane >> 4) * 4 + i;
-        if (cm >= M) continue;
-        short v = f2bf_u16(acc[rg][t][i]);
-        if (prev_out)
-          v = act_grad_u16(v, prev_out[(int64_t)cm * K + ck], prev_act);
-        dX[(int64_t)cm * K + ck] = v;
-      }
-    }
-  }
+  for (int rg = 0; rg < 2; ++rg)
+    dx_store_tile(acc[rg], lane, m0 + rg * 16, c0, kt, M, K, dX, prev_out,
+                  prev_act);
 }
 
-// LDS-staged dW: block = (16-row N tile) x (64-col K group) x (128-row M
-// chunk). G[128,16] and A[128,64] chunks are staged with coalesced row
-// loads; the four waves compute the four 16x16 k-subtiles from LDS
-// (column reads land in distinct banks: 16 consecutive bf16 = 32 B).
-// Replaces the 8-scalar-strided-load fragments (31 us -> target <10 us on
-// the 8192x512x256 layer). fp32 atomic accumulate; fused dbias.
+// dW for narrow N (< 64): block = (16-row N tile) x (64-col K group) x
+// (128-row M chunk). G[128,16] and A[128,64] chunks are staged with
+// coalesced row loads into padded LDS rows; the four waves compute the four
+// 16x16 k-subtiles with scalar column reads (16 consecutive bf16 = 32 B per
+// row). fp32 atomic accumulate, one flush per chunk; fused dbias.
 __global__ void k_linear_dw_lds(const short* __restrict__ G,
                                 const short* __restrict__ A, int M, int N,
                                 int K, float* __restrict__ dW,
@@ -430,7 +463,6 @@ __global__ void k_linear_dw_lds(const short* __restrict__ G,
   constexpr int APAD = 8;      // LDS row pad (banks)
   __shared__ short a_l[CH][KG + APAD];
   __shared__ short g_l[CH][16 + APAD];
-  __shared__ float bred[16];
 
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
@@ -466,7 +498,7 @@ __global__ void k_linear_dw_lds(const short* __restrict__ G,
   const int col_a = kw + (lane & 15);
   const int col_g = lane & 15;
   const int kgrp = (lane >> 4) * 8;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[1] = {};
   float bsum = 0.0f;
   const bool do_bias = (dbias != nullptr) && (k0 == 0) && (wave == 0);
 #pragma unroll
@@ -478,121 +510,24 @@ __global__ void k_linear_dw_lds(const short* __restrict__ G,
       gfrag[i] = g_l[m][col_g];
       afrag[i] = a_l[m][col_a];
     }
-    acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfrag, afrag, acc, 0, 0,
-                                                  0);
-    if (do_bias) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) bsum += bf2f_u16(gfrag[i]);
-    }
+    acc[0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfrag, afrag, acc[0], 0,
+                                                     0, 0);
+    if (do_bias) bsum = dbias_add_frag(bsum, gfrag);
   }
-  const int ck = k0 + col_a;
-  if (ck < K) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int cn = n0 + (lane >> 4) * 4 + i;
-      if (cn >= N) continue;
-      atomicAdd(&dW[(int64_t)cn * K + ck], acc[i]);
-    }
-  }
-  if (do_bias) {
-    float v = bsum;
-    for (int off = 16; off < 64; off += 16)
-      v += __shfl(bsum, (lane & 15) + off);
-    if (lane < 16) {
-      int cn = n0 + lane;
-      if (cn < N) atomicAdd(&dbias[cn], v);
-    }
-  }
+  dw_flush<1>(acc, lane, n0, k0 + kw, N, K, dW);
+  if (do_bias) dbias_reduce_add(bsum, lane, n0, N, dbias);
 }
 
-// 64-col-G variant: block = 64n x 64k x 128m. The 16-col version above
-// restages the A chunk once per 16-row N tile (N=512 -> 32x = 252 MB of
-// A traffic on the 8192x512x480 layer); staging G and A as 64-wide tiles
-// cuts that to N/64 restages (63 MB) + K/64 G restages. Wave w owns
-// output rows n0+16w..+16, all 64 k columns.
-__global__ void k_linear_dw_lds64(const short* __restrict__ G,
-                                  const short* __restrict__ A, int M, int N,
-                                  int K, float* __restrict__ dW,
-                                  float* __restrict__ dbias) {
-  constexpr int CH = 128;
-  __shared__ short a_l[CH][64 + 8];
-  __shared__ short g_l[CH][64 + 8];
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int tid = threadIdx.x;
-  const int kgroups = (K + 63) / 64;
-  const int ngroups = (N + 63) / 64;
-  const int tile_id = blockIdx.x % (ngroups * kgroups);
-  const int chunk = blockIdx.x / (ngroups * kgroups);
-  const int n0 = (tile_id / kgroups) * 64;
-  const int k0 = (tile_id % kgroups) * 64;
-  const int mbeg = chunk * CH;
-  {
-    const int r = tid >> 3, seg = tid & 7;
-    for (int it = 0; it < CH / 32; ++it) {
-      int rr = it * 32 + r;
-      *reinterpret_cast<bf16x8*>(&a_l[rr][seg * 8]) =
-          load_frag_row(A, mbeg + rr, k0 + seg * 8, M, K);
-      *reinterpret_cast<bf16x8*>(&g_l[rr][seg * 8]) =
-          load_frag_row(G, mbeg + rr, n0 + seg * 8, M, N);
-    }
-  }
-  __syncthreads();
-  const int col_g = wave * 16 + (lane & 15);
-  const int kgrp = (lane >> 4) * 8;
-  f32x4 acc[4] = {};
-  float bsum = 0.0f;
-  const bool do_bias = (dbias != nullptr) && (k0 == 0);
-#pragma unroll
-  for (int ms = 0; ms < CH; ms += 32) {
-    bf16x8 gfrag;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) gfrag[i] = g_l[ms + kgrp + i][col_g];
-    if (do_bias) {
-#pragma unroll
-      for (int i = 0; i < 8; ++i) bsum += bf2f_u16(gfrag[i]);
-    }
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-      bf16x8 afrag;
-#pragma unroll
-      for (int i = 0; i < 8; ++i)
-        afrag[i] = a_l[ms + kgrp + i][t * 16 + (lane & 15)];
-      acc[t] =
-          __builtin_amdgcn_mfma_f32_16x16x32_bf16(gfrag, afrag, acc[t], 0,
-                                                  0, 0);
-    }
-  }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int ck = k0 + t * 16 + (lane & 15);
-    if (ck >= K) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int cn = n0 + wave * 16 + (lane >> 4) * 4 + i;
-      if (cn >= N) continue;
-      atomicAdd(&dW[(int64_t)cn * K + ck], acc[t][i]);
-    }
-  }
-  if (do_bias) {
-    // each wave owns 16 distinct bias columns (n0 + 16w + lane%16):
-    // reduce the 4 kgrp groups' partials within the wave, one atomic each
-    float v = bsum;
-    for (int off = 16; off < 64; off += 16)
-      v += __shfl(bsum, (lane & 15) + off);
-    const int cn = n0 + wave * 16 + (lane & 15);
-    if (lane < 16 && cn < N) atomicAdd(&dbias[cn], v);
-  }
-}
-
-// Multi-chunk dW: same 64n x 64k tile as lds64, but (a) each MFMA
-// fragment comes from two transposed LDS reads of row-major G and A
-// chunks (layout and bank arithmetic: trt_off above; the chunks are
-// stored as they are loaded, one 16-B store per 16-B global load), and
-// (b) each block accumulates `cpb` consecutive 128-row M chunks in
-// registers before its single atomic flush. The per-chunk atomic flush
-// was the real bound: 64 chunks x N*K fp32 atomics = 63 MB of atomic
-// writes on the 8192x512x480 layer (~31 us of the 60 us).
+// dW for N >= 64: block = 64n x 64k x (cpb x 128)m; wave w owns output
+// rows n0+16w..+16, all 64 k columns. With 64-wide tiles the A chunk is
+// restaged N/64 times instead of N/16 (252 MB -> 63 MB of A traffic on the
+// 8192x512x480 layer). (a) Each MFMA fragment comes from two transposed
+// LDS reads of row-major G and A chunks (layout and bank arithmetic:
+// trt_off above; the chunks are stored as they are loaded, one 16-B store
+// per 16-B global load), and (b) each block accumulates `cpb` consecutive
+// 128-row M chunks in registers before its single atomic flush. A
+// per-chunk atomic flush was the real bound: 64 chunks x N*K fp32 atomics
+// = 63 MB of atomic writes on the 8192x512x480 layer (~31 us of 60 us).
 // All 128 rows of both tiles are rewritten every chunk (zero-filled past
 // M, N and K by load_frag_row), so a ragged chunk never sums a stale row
 // of the chunk before it.
@@ -610,16 +545,13 @@ __global__ void k_linear_dw_lds64t(const short* __restrict__ G,
   __shared__ __attribute__((aligned(16))) short g_s[CH * TRT_COLS];
   const int lane = threadIdx.x & 63;
   const int wave = threadIdx.x >> 6;
-  const int tid = threadIdx.x;
   const int kgroups = (K + 63) / 64;
   const int ngroups = (N + 63) / 64;
   const int tile_id = blockIdx.x % (ngroups * kgroups);
   const int chunk0 = (blockIdx.x / (ngroups * kgroups)) * cpb;
   const int n0 = (tile_id / kgroups) * 64;
   const int k0 = (tile_id % kgroups) * 64;
-  // staging: thread -> row tid/8 of each 32-row slab, 16-B segment tid%8
-  const int st_r = tid >> 3, st_seg = tid & 7;
-  const int st_off = trt_off(st_r, st_seg * 8);
+  const TrtStager stg(threadIdx.x);
   const int g_off = trt_lane_off(lane, wave * 16);
   int a_off[4];
 #pragma unroll
@@ -635,23 +567,19 @@ __global__ void k_linear_dw_lds64t(const short* __restrict__ G,
     bf16x8 va[CH / 32], vg[CH / 32];
 #pragma unroll
     for (int it = 0; it < CH / 32; ++it) {
-      const int m = mbeg + it * 32 + st_r;
-      va[it] = load_frag_row(A, m, k0 + st_seg * 8, M, K);
-      vg[it] = load_frag_row(G, m, n0 + st_seg * 8, M, N);
+      va[it] = stg.load(A, mbeg, it, k0, M, K);
+      vg[it] = stg.load(G, mbeg, it, n0, M, N);
     }
 #pragma unroll
     for (int it = 0; it < CH / 32; ++it) {
-      *reinterpret_cast<bf16x8*>(&a_s[it * 32 * TRT_COLS + st_off]) = va[it];
-      *reinterpret_cast<bf16x8*>(&g_s[it * 32 * TRT_COLS + st_off]) = vg[it];
+      stg.store(a_s, it, va[it]);
+      stg.store(g_s, it, vg[it]);
     }
     __syncthreads();
 #pragma unroll
     for (int ms = 0; ms < CH; ms += 32) {
       bf16x8 gfrag = trt_frag(&g_s[ms * TRT_COLS + g_off]);
-      if (do_bias) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) bsum += bf2f_u16(gfrag[i]);
-      }
+      if (do_bias) bsum = dbias_add_frag(bsum, gfrag);
 #pragma unroll
       for (int t = 0; t < 4; ++t) {
         bf16x8 afrag = trt_frag(&a_s[ms * TRT_COLS + a_off[t]]);
@@ -661,24 +589,8 @@ __global__ void k_linear_dw_lds64t(const short* __restrict__ G,
       }
     }
   }
-#pragma unroll
-  for (int t = 0; t < 4; ++t) {
-    const int ck = k0 + t * 16 + (lane & 15);
-    if (ck >= K) continue;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      int cn = n0 + wave * 16 + (lane >> 4) * 4 + i;
-      if (cn >= N) continue;
-      atomicAdd(&dW[(int64_t)cn * K + ck], acc[t][i]);
-    }
-  }
-  if (do_bias) {
-    float v = bsum;
-    for (int off = 16; off < 64; off += 16)
-      v += __shfl(bsum, (lane & 15) + off);
-    const int cn = n0 + wave * 16 + (lane & 15);
-    if (lane < 16 && cn < N) atomicAdd(&dbias[cn], v);
-  }
+  dw_flush<4>(acc, lane, n0 + wave * 16, k0, N, K, dW);
+  if (do_bias) dbias_reduce_add(bsum, lane, n0 + wave * 16, N, dbias);
 }
 
 // ------------------------------------------------------------------
@@ -1198,18 +1110,19 @@ torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w_bf16,
   TORCH_CHECK(!bias.defined() || bias.numel() == 0 ||
                   (bias.numel() == N && bias.is_contiguous()),
               "linear_fwd: bias must be empty or contiguous [N]");
+  TORCH_CHECK(variant >= -1 && variant <= 1, "linear_fwd: variant must be "
+              "-1 (automatic), 0 (MT=1) or 1 (MT=2), got ", variant);
   auto out = torch::empty({M, N}, x.options());
   int tiles_n = (N + 63) / 64;
   const float* bp =
       bias.defined() && bias.numel() ? bias.data_ptr<float>() : nullptr;
-  if (variant < 0) variant = 0;  // MT=1 measured fastest across the zoo
   if (variant == 1) {
     int blocks = ((M + 127) / 128) * tiles_n;
-    k_linear_fwd_t<2><<<blocks, 256, 0, dense_stream()>>>(
+    k_linear_fwd_t<2><<<blocks, 256, 0, current_hip_stream()>>>(
         bf_ptr(x), bf_ptr(w_bf16), bp, M, N, K, (int)act, bf_ptr_mut(out));
-  } else {
+  } else {  // -1, 0: MT=1 measured fastest across the zoo
     int blocks = ((M + 63) / 64) * tiles_n;
-    k_linear_fwd_t<1><<<blocks, 256, 0, dense_stream()>>>(
+    k_linear_fwd_t<1><<<blocks, 256, 0, current_hip_stream()>>>(
         bf_ptr(x), bf_ptr(w_bf16), bp, M, N, K, (int)act, bf_ptr_mut(out));
   }
   return out;
@@ -1243,12 +1156,12 @@ torch::Tensor linear_dx(torch::Tensor g, torch::Tensor w_bf16,
   if (N >= 128) {
     // wide GEMM-K: strided W-column loads dominate -> LDS-staged variant
     int blocks = ((M + 127) / 128) * tiles_k;
-    k_linear_dx_lds<<<blocks, 256, 0, dense_stream()>>>(
+    k_linear_dx_lds<<<blocks, TRT_STAGE_THREADS, 0, current_hip_stream()>>>(
         bf_ptr(g), bf_ptr(w_bf16), M, N, K, bf_ptr_mut(dx), pp,
         (int)prev_act);
   } else {
     int blocks = ((M + 63) / 64) * tiles_k;
-    k_linear_dx<<<blocks, 256, 0, dense_stream()>>>(
+    k_linear_dx<<<blocks, 256, 0, current_hip_stream()>>>(
         bf_ptr(g), bf_ptr(w_bf16), M, N, K, bf_ptr_mut(dx), pp,
         (int)prev_act);
   }
@@ -1257,23 +1170,38 @@ torch::Tensor linear_dx(torch::Tensor g, torch::Tensor w_bf16,
 
 static void zero_f32_launch(float* p, int64_t n) {
   k_zero_f32d<<<(int)std::clamp<int64_t>((n / 4 + 255) / 256, 1, 1024), 256,
-                0, dense_stream()>>>(p, n);
+                0, current_hip_stream()>>>(p, n);
 }
 
+// Shared body of linear_dw (ws undefined: allocated here) and linear_dw_out
+// (ws = the caller's flat [N*K (+ N)] slice); `op` names the binding in the
+// messages. Every check runs before anything is zero-filled or launched.
 // zero = false: the caller has cleared ws already (one zero_f32 over a
 // whole tower's adjacent slices); the kernels only accumulate.
 static std::tuple<torch::Tensor, torch::Tensor> linear_dw_impl(
-    torch::Tensor g, torch::Tensor x, torch::Tensor ws, bool want_bias,
-    int64_t variant, bool zero = true) {
-  check_bf16_matrix(g, "linear_dw", "g");
-  check_bf16_matrix(x, "linear_dw", "x");
-  TORCH_CHECK(g.size(0) == x.size(0), "linear_dw: g has ", g.size(0),
+    const char* op, torch::Tensor g, torch::Tensor x, torch::Tensor ws,
+    bool want_bias, int64_t variant, bool zero) {
+  check_bf16_matrix(g, op, "g");
+  check_bf16_matrix(x, op, "x");
+  TORCH_CHECK(g.size(0) == x.size(0), op, ": g has ", g.size(0),
               " rows but x has ", x.size(0));
+  TORCH_CHECK(variant == -1 || variant == 0 || variant == 2, op,
+              ": variant must be -1 (automatic), 0 (k_linear_dw_lds) or 2 "
+              "(k_linear_dw_lds64t), got ", variant);
   int M = g.size(0), N = g.size(1), K = x.size(1);
+  int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
+  if (ws.defined()) {
+    TORCH_CHECK(ws.is_cuda() && ws.is_contiguous() &&
+                    ws.scalar_type() == torch::kFloat32 &&
+                    ws.numel() == ws_len,
+                op, ": ws must be a contiguous fp32 GPU tensor of ", ws_len,
+                " elements");
+  } else {
+    ws = torch::empty({ws_len}, g.options().dtype(torch::kFloat32));
+  }
   // one fill-kernel zero for dW + dbias (cheaper than torch's fill
   // machinery; hipMemsetAsync is avoided: memset nodes recorded during
   // hipGraph capture were observed not to replay)
-  int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
   if (zero) zero_f32_launch(ws.data_ptr<float>(), ws_len);
   auto dw = ws.narrow(0, 0, (int64_t)N * K).view({N, K});
   auto db = want_bias ? ws.narrow(0, (int64_t)N * K, N) : torch::Tensor();
@@ -1286,16 +1214,13 @@ static std::tuple<torch::Tensor, torch::Tensor> linear_dw_impl(
     // atomic flush volume drops by cpb x
     int tiles = ((N + 63) / 64) * ((K + 63) / 64);
     int cpb = std::max(1, (int)((int64_t)m_chunks * tiles / 512));
-    int chunk_blocks = (m_chunks + cpb - 1) / cpb;
-    k_linear_dw_lds64t<<<tiles * chunk_blocks, 256, 0, dense_stream()>>>(
+    int blocks = tiles * ((m_chunks + cpb - 1) / cpb);
+    k_linear_dw_lds64t<<<blocks, TRT_STAGE_THREADS, 0,
+                         current_hip_stream()>>>(
         bf_ptr(g), bf_ptr(x), M, N, K, cpb, dw.data_ptr<float>(), dbp);
-  } else if (variant == 1) {
-    int tiles = ((N + 63) / 64) * ((K + 63) / 64);
-    k_linear_dw_lds64<<<tiles * m_chunks, 256, 0, dense_stream()>>>(
-        bf_ptr(g), bf_ptr(x), M, N, K, dw.data_ptr<float>(), dbp);
   } else {
     int tiles = ((N + 15) / 16) * ((K + 63) / 64);
-    k_linear_dw_lds<<<tiles * m_chunks, 256, 0, dense_stream()>>>(
+    k_linear_dw_lds<<<tiles * m_chunks, 256, 0, current_hip_stream()>>>(
         bf_ptr(g), bf_ptr(x), M, N, K, dw.data_ptr<float>(), dbp);
   }
   return {dw, db};
@@ -1305,12 +1230,8 @@ std::tuple<torch::Tensor, torch::Tensor> linear_dw(torch::Tensor g,
                                                    torch::Tensor x,
                                                    bool want_bias,
                                                    int64_t variant) {
-  check_bf16_matrix(g, "linear_dw", "g");
-  check_bf16_matrix(x, "linear_dw", "x");
-  int N = g.size(1), K = x.size(1);
-  int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
-  auto ws = torch::empty({ws_len}, g.options().dtype(torch::kFloat32));
-  return linear_dw_impl(g, x, ws, want_bias, variant);
+  return linear_dw_impl("linear_dw", g, x, torch::Tensor(), want_bias,
+                        variant, true);
 }
 
 // dW/db written into a caller-provided flat [N*K + N] workspace — a view
@@ -1323,14 +1244,8 @@ std::tuple<torch::Tensor, torch::Tensor> linear_dw_out(torch::Tensor g,
                                                        bool want_bias,
                                                        int64_t variant,
                                                        bool zero) {
-  TORCH_CHECK(ws.is_cuda() && ws.is_contiguous() &&
-              ws.scalar_type() == torch::kFloat32);
-  check_bf16_matrix(g, "linear_dw_out", "g");
-  check_bf16_matrix(x, "linear_dw_out", "x");
-  int N = g.size(1), K = x.size(1);
-  int64_t ws_len = (int64_t)N * K + (want_bias ? N : 0);
-  TORCH_CHECK(ws.numel() == ws_len, "linear_dw_out: workspace size");
-  return linear_dw_impl(g, x, ws, want_bias, variant, zero);
+  TORCH_CHECK(ws.defined(), "linear_dw_out: ws is undefined");
+  return linear_dw_impl("linear_dw_out", g, x, ws, want_bias, variant, zero);
 }
 
 // clear any contiguous fp32 1-D tensor with the capture-safe fill kernel
@@ -1356,7 +1271,7 @@ torch::Tensor pad_cast_bf16(torch::Tensor x, int64_t k_pad) {
   if (M == 0 || k_pad == 0) return y;
   int64_t groups = M * ((k_pad + 7) / 8);
   int blocks = (int)std::clamp<int64_t>((groups + 255) / 256, 1, 4096);
-  k_pad_cast_bf16<<<blocks, 256, 0, dense_stream()>>>(
+  k_pad_cast_bf16<<<blocks, 256, 0, current_hip_stream()>>>(
       x.data_ptr<float>(), M, (int)K, (int)k_pad, bf_ptr_mut(y));
   return y;
 }
@@ -1375,7 +1290,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> resln_fwd(
   TORCH_CHECK(N == 16 || N == 32 || N == 64, "resln: N must be 16/32/64");
   int blocks = (int)std::min<int64_t>((M + 255) / 256, 4096);
 #define RESLN_FWD(NV) \
-  k_resln_fwd<NV><<<blocks, 256, 0, dense_stream()>>>( \
+  k_resln_fwd<NV><<<blocks, 256, 0, current_hip_stream()>>>( \
       bf_ptr(x), bf_ptr(a), gamma.data_ptr<float>(), \
       beta.data_ptr<float>(), M, (float)eps, bf_ptr_mut(y), \
       bf_ptr_mut(z), stats.data_ptr<float>())
@@ -1395,7 +1310,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> resln_bwd(
   auto opts = gamma.options();
   auto dgamma = torch::empty({N}, opts);
   auto dbeta = torch::empty({N}, opts);
-  auto stream = dense_stream();
+  auto stream = current_hip_stream();
   k_zero_f32d<<<1, 64, 0, stream>>>(dgamma.data_ptr<float>(), N);
   k_zero_f32d<<<1, 64, 0, stream>>>(dbeta.data_ptr<float>(), N);
   if (M == 0) return {dz, dgamma, dbeta};
@@ -1425,7 +1340,7 @@ void dense_adam(torch::Tensor w, torch::Tensor g, torch::Tensor m,
                     ? reinterpret_cast<short*>(w16.data_ptr<at::BFloat16>())
                     : nullptr;
   int blocks = (int)std::min<int64_t>((n + 255) / 256, 4096);
-  k_dense_adam<<<blocks, 256, 0, dense_stream()>>>(
+  k_dense_adam<<<blocks, 256, 0, current_hip_stream()>>>(
       w.data_ptr<float>(), g.data_ptr<float>(), m.data_ptr<float>(),
       v.data_ptr<float>(), w16p, powers.data_ptr<float>(), n, (float)lr,
       (float)beta1, (float)beta2, (float)eps, (float)gscale);
@@ -1435,7 +1350,7 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor out, int64_t act) {
   auto g = torch::empty_like(dy);
   int64_t n = dy.numel();
   int blocks = (int)std::min<int64_t>((n / 8 + 255) / 256, 4096);
-  k_act_bwd<<<std::max(blocks, 1), 256, 0, dense_stream()>>>(
+  k_act_bwd<<<std::max(blocks, 1), 256, 0, current_hip_stream()>>>(
       bf_ptr(dy), bf_ptr(out), n, (int)act, bf_ptr_mut(g));
   return g;
 }
@@ -1449,7 +1364,7 @@ torch::Tensor interact_fwd(torch::Tensor feats, int64_t p_pad) {
   auto out = torch::empty({B, p_pad}, feats.options());
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)F * D * sizeof(short);
-  k_interact_fwd<<<blocks, 256, lds, dense_stream()>>>(
+  k_interact_fwd<<<blocks, 256, lds, current_hip_stream()>>>(
       bf_ptr(feats), B, F, D, P, (int)p_pad, bf_ptr_mut(out));
   return out;
 }
@@ -1462,7 +1377,7 @@ torch::Tensor interact_bwd(torch::Tensor grad, torch::Tensor feats) {
   auto dfeats = torch::empty_like(feats);
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)(F * D + ((P + 7) & ~7)) * sizeof(short);
-  k_interact_bwd<<<blocks, 256, lds, dense_stream()>>>(
+  k_interact_bwd<<<blocks, 256, lds, current_hip_stream()>>>(
       bf_ptr(grad.contiguous()), bf_ptr(feats), B, F, D, P, P_pad,
       bf_ptr_mut(dfeats));
   return dfeats;
@@ -1479,7 +1394,7 @@ torch::Tensor interact_cat_fwd(torch::Tensor bot, torch::Tensor emb,
   auto out = torch::empty({B, D + p_pad}, emb.options());
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)F * D * sizeof(short);
-  k_interact_cat_fwd<<<blocks, 256, lds, dense_stream()>>>(
+  k_interact_cat_fwd<<<blocks, 256, lds, current_hip_stream()>>>(
       bf_ptr(bot), bf_ptr(emb), B, Fe, D, P, (int)p_pad, bf_ptr_mut(out));
   return out;
 }
@@ -1495,7 +1410,7 @@ std::tuple<torch::Tensor, torch::Tensor> interact_cat_bwd(
   auto demb = torch::empty_like(emb);
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)(F * D + ((P + 7) & ~7)) * sizeof(short);
-  k_interact_cat_bwd<<<blocks, 256, lds, dense_stream()>>>(
+  k_interact_cat_bwd<<<blocks, 256, lds, current_hip_stream()>>>(
       bf_ptr(grad.contiguous()), bf_ptr(bot), bf_ptr(emb), B, Fe, D, P,
       P_pad, bf_ptr_mut(dbot), bf_ptr_mut(demb));
   return {dbot, demb};
@@ -1507,7 +1422,7 @@ std::tuple<torch::Tensor, torch::Tensor> l2norm_fwd(torch::Tensor x,
   int M = x.size(0), N = x.size(1);
   auto y = torch::empty_like(x);
   auto inv = torch::empty({M}, x.options().dtype(torch::kFloat32));
-  k_l2norm_fwd<<<(M + 3) / 4, 256, 0, dense_stream()>>>(
+  k_l2norm_fwd<<<(M + 3) / 4, 256, 0, current_hip_stream()>>>(
       bf_ptr(x), M, N, (float)eps, bf_ptr_mut(y), inv.data_ptr<float>());
   return {y, inv};
 }
@@ -1516,7 +1431,7 @@ torch::Tensor l2norm_bwd(torch::Tensor dy, torch::Tensor y,
                          torch::Tensor inv) {
   int M = y.size(0), N = y.size(1);
   auto dx = torch::empty_like(y);
-  k_l2norm_bwd<<<(M + 3) / 4, 256, 0, dense_stream()>>>(
+  k_l2norm_bwd<<<(M + 3) / 4, 256, 0, current_hip_stream()>>>(
       bf_ptr(dy.contiguous()), bf_ptr(y), inv.data_ptr<float>(), M, N,
       bf_ptr_mut(dx));
   return dx;

@@ -25,17 +25,7 @@
 // value-row elements (coalesced); blocks are multiples of 64; atomics are
 // device-scope by default (per-XCD L2 non-coherence is safe).
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-
-// current-stream accessor (ROCm ATen name)
-static inline hipStream_t current_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
-
-#include <cstdint>
+#include "hip_common.h"
 
 #define DEV_INLINE __device__ __forceinline__
 
@@ -1187,7 +1177,7 @@ torch::Tensor ht_lookup_insert(
   int n = keys.numel();
   auto out = torch::empty({n}, keys.options().dtype(torch::kInt32));
   if (n == 0) return out;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   int dim = values.size(1);
   k_lookup_insert<<<n_blocks(n), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(),
@@ -1221,7 +1211,7 @@ torch::Tensor ht_dedup_a(torch::Tensor keys, torch::Tensor ht_keys,
                          torch::Tensor occ_entry, torch::Tensor error_flag) {
   int64_t nnz = keys.numel();
   if (nnz == 0) return m_counter;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_dedup_pass_a<<<n_blocks(nnz), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
       ht_epoch.data_ptr<int32_t>(), ht_compact.data_ptr<int32_t>(),
@@ -1246,7 +1236,7 @@ torch::Tensor ht_dedup_b(torch::Tensor compact_entry, torch::Tensor uniq_keys,
   int n = uniq_keys.numel();
   auto slots = torch::empty({n}, ht_slot.options());
   if (n == 0) return slots;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_dedup_pass_b<<<n_blocks(n), kBlock, 0, stream>>>(
       compact_entry.data_ptr<int64_t>(), uniq_keys.data_ptr<int64_t>(), n,
       opt_ptr<int32_t>(m_dev), ht_slot.data_ptr<int32_t>(),
@@ -1261,12 +1251,12 @@ torch::Tensor ht_dedup_b(torch::Tensor compact_entry, torch::Tensor uniq_keys,
 }
 
 void bump_epoch(torch::Tensor epoch_dev, torch::Tensor step_dev) {
-  k_bump_epoch<<<1, 64, 0, current_stream()>>>(
+  k_bump_epoch<<<1, 64, 0, current_hip_stream()>>>(
       epoch_dev.data_ptr<int32_t>(), step_dev.data_ptr<int64_t>());
 }
 
 void bump_epoch_only(torch::Tensor epoch_dev) {
-  k_bump_epoch_only<<<1, 64, 0, current_stream()>>>(
+  k_bump_epoch_only<<<1, 64, 0, current_hip_stream()>>>(
       epoch_dev.data_ptr<int32_t>());
 }
 
@@ -1281,7 +1271,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> route_pad(
   auto send_cnt = torch::empty({(int64_t)total}, opts_i32);
   auto route_pos = torch::empty({(int64_t)n_cap}, opts_i32);
   auto cursor = torch::empty({world}, opts_i32);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_route_fill<<<n_blocks(total), kBlock, 0, stream>>>(
       send_keys.data_ptr<int64_t>(), send_cnt.data_ptr<int32_t>(),
       cursor.data_ptr<int32_t>(), total, (int)world);
@@ -1298,7 +1288,7 @@ torch::Tensor slots_gather_pad(torch::Tensor inverse, torch::Tensor slots) {
   int64_t nnz = inverse.numel();
   auto out = torch::empty({nnz}, slots.options());
   if (nnz == 0) return out;
-  k_slots_gather_pad<<<n_blocks(nnz), kBlock, 0, current_stream()>>>(
+  k_slots_gather_pad<<<n_blocks(nnz), kBlock, 0, current_hip_stream()>>>(
       inverse.data_ptr<int32_t>(), slots.data_ptr<int32_t>(), (int)nnz,
       out.data_ptr<int32_t>());
   return out;
@@ -1308,7 +1298,7 @@ torch::Tensor cnt_sum_pad(torch::Tensor inverse, torch::Tensor cnt,
                           int64_t m_cap) {
   int64_t nnz = inverse.numel();
   auto out = torch::empty({m_cap}, cnt.options());
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   zero_fill(out.data_ptr<int32_t>(), m_cap, stream);
   if (nnz)
     k_cnt_sum_pad<<<n_blocks(nnz), kBlock, 0, stream>>>(
@@ -1322,7 +1312,7 @@ torch::Tensor rows_segsum_pad(torch::Tensor grad, torch::Tensor inverse,
   int64_t nnz = inverse.numel();
   int dim = grad.size(1);
   auto out = torch::empty({m_cap, (int64_t)dim}, grad.options());
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   zero_fill(out.data_ptr<float>(), m_cap * dim, stream);
   if (nnz)
     k_rows_segsum_pad<<<n_blocks(nnz * dim), kBlock, 0, stream>>>(
@@ -1339,7 +1329,7 @@ torch::Tensor gather_host_rows(torch::Tensor host_src, torch::Tensor rows) {
   auto out = torch::empty({m, (int64_t)dim},
                           rows.options().dtype(torch::kFloat32));
   if (m == 0) return out;
-  k_gather_host_rows<<<n_blocks(m * dim), kBlock, 0, current_stream()>>>(
+  k_gather_host_rows<<<n_blocks(m * dim), kBlock, 0, current_hip_stream()>>>(
       host_src.data_ptr<float>(), rows.data_ptr<int64_t>(), m, dim,
       out.data_ptr<float>());
   return out;
@@ -1352,7 +1342,7 @@ void scatter_host_rows(torch::Tensor src, torch::Tensor rows,
   int64_t m = rows.numel();
   int dim = host_dst.size(1);
   if (m == 0) return;
-  k_scatter_host_rows<<<n_blocks(m * dim), kBlock, 0, current_stream()>>>(
+  k_scatter_host_rows<<<n_blocks(m * dim), kBlock, 0, current_hip_stream()>>>(
       src.data_ptr<float>(), rows.data_ptr<int64_t>(), m, dim,
       host_dst.data_ptr<float>());
 }
@@ -1361,7 +1351,7 @@ torch::Tensor compose_i32(torch::Tensor inv_in, torch::Tensor lut) {
   int64_t nnz = inv_in.numel();
   auto out = torch::empty({nnz}, inv_in.options());
   if (nnz == 0) return out;
-  k_compose_i32<<<n_blocks(nnz), kBlock, 0, current_stream()>>>(
+  k_compose_i32<<<n_blocks(nnz), kBlock, 0, current_hip_stream()>>>(
       inv_in.data_ptr<int32_t>(), lut.data_ptr<int32_t>(), (int)nnz,
       out.data_ptr<int32_t>());
   return out;
@@ -1372,7 +1362,7 @@ torch::Tensor rows_to_padded(torch::Tensor src, torch::Tensor route_pos,
   int n_cap = route_pos.numel();
   int dim = src.size(1);
   auto dst = torch::empty({out_rows, (int64_t)dim}, src.options());
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   zero_fill(dst.data_ptr<float>(), out_rows * dim, stream);
   k_rows_to_padded<<<n_blocks((int64_t)n_cap * dim), kBlock, 0, stream>>>(
       src.data_ptr<float>(), route_pos.data_ptr<int32_t>(),
@@ -1389,7 +1379,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ht_dedup_c(
   auto rank = torch::empty({nnz}, ht_compact.options());
   auto counts = torch::empty({m}, ht_compact.options());
   if (nnz == 0) return {inverse, counts, rank};
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   zero_fill(counts.data_ptr<int32_t>(), m, stream);
   k_dedup_pass_c<<<n_blocks(nnz), kBlock, 0, stream>>>(
       opt_ptr<int64_t>(keys), occ_entry.data_ptr<int64_t>(), (int)nnz,
@@ -1403,7 +1393,7 @@ torch::Tensor csr_scatter(torch::Tensor inverse, torch::Tensor rank,
   int64_t nnz = inverse.numel();
   auto order = torch::empty({nnz}, inverse.options());
   if (nnz == 0) return order;
-  k_csr_scatter<<<n_blocks(nnz), kBlock, 0, current_stream()>>>(
+  k_csr_scatter<<<n_blocks(nnz), kBlock, 0, current_hip_stream()>>>(
       inverse.data_ptr<int32_t>(), rank.data_ptr<int32_t>(), (int)nnz,
       bounds.data_ptr<int32_t>(), order.data_ptr<int32_t>(),
       error_flag.data_ptr<int32_t>());
@@ -1416,7 +1406,7 @@ torch::Tensor csr_order(torch::Tensor inverse, torch::Tensor bounds,
   auto order = torch::empty({nnz}, inverse.options());
   auto cursor = torch::zeros({m}, inverse.options());
   if (nnz == 0) return order;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_csr_order<<<n_blocks(nnz), kBlock, 0, stream>>>(
       inverse.data_ptr<int32_t>(), (int)nnz, bounds.data_ptr<int32_t>(),
       cursor.data_ptr<int32_t>(), order.data_ptr<int32_t>());
@@ -1430,7 +1420,7 @@ void ht_insert_bulk(torch::Tensor keys, torch::Tensor slots,
                     torch::Tensor entry_counter, torch::Tensor error_flag) {
   int n = keys.numel();
   if (n == 0) return;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_insert_bulk<<<n_blocks(n), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
       freqs.defined() && freqs.numel() ? freqs.data_ptr<int32_t>() : nullptr,
@@ -1452,7 +1442,7 @@ std::tuple<torch::Tensor, torch::Tensor> ht_lookup(torch::Tensor keys,
                    ? torch::empty({n}, keys.options().dtype(torch::kInt64))
                    : torch::Tensor();
   if (n == 0) return {slots, entry};
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_lookup<<<n_blocks(n), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(), n, ht_keys.data_ptr<int64_t>(),
       ht_slot.data_ptr<int32_t>(), ht_keys.numel() - 1,
@@ -1472,7 +1462,7 @@ ht_export(torch::Tensor ht_keys, torch::Tensor ht_slot, torch::Tensor ht_freq,
   auto out_versions = torch::empty({n_entries}, opts_i64);
   auto cursor = torch::zeros({1}, opts_i32);
   if (n_entries > 0) {
-    auto stream = current_stream();
+    auto stream = current_hip_stream();
     k_export_scan<<<n_blocks(ht_keys.numel()), kBlock, 0, stream>>>(
         ht_keys.data_ptr<int64_t>(), ht_slot.data_ptr<int32_t>(),
         ht_freq.data_ptr<int32_t>(), ht_version.data_ptr<int64_t>(),
@@ -1492,7 +1482,7 @@ torch::Tensor ev_gather(torch::Tensor values, torch::Tensor default_values,
   int dim = values.size(1);
   auto out = torch::empty({m, dim}, values.options().dtype(out_dtype));
   if (m == 0) return out;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   int64_t total = (int64_t)m * dim;
   if (out_dtype == torch::kBFloat16) {
     k_gather<__hip_bfloat16><<<n_blocks(total), kBlock, 0, stream>>>(
@@ -1521,7 +1511,7 @@ torch::Tensor pooled_fwd(torch::Tensor values, torch::Tensor default_values,
   int dim = values.size(1);
   auto out = torch::empty({batch, dim}, values.options().dtype(out_dtype));
   if (batch == 0) return out;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   int64_t total = (int64_t)batch * dim;
   const float* wptr =
       weights.defined() && weights.numel() ? weights.data_ptr<float>()
@@ -1553,7 +1543,7 @@ torch::Tensor pooled_bwd(torch::Tensor grad_out, torch::Tensor inverse,
   auto grad_unique = torch::zeros(
       {m, dim}, grad_out.options().dtype(torch::kFloat32));
   if (batch == 0 || m == 0) return grad_unique;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   int64_t total = (int64_t)batch * dim;
   const float* wptr =
       weights.defined() && weights.numel() ? weights.data_ptr<float>()
@@ -1584,7 +1574,7 @@ torch::Tensor group_pooled_fwd(
                           values.options().dtype(out_dtype));
   int64_t total = batch * n_tables * dim;
   if (total == 0) return out;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   const float* wptr =
       weights.defined() && weights.numel() ? weights.data_ptr<float>()
                                            : nullptr;
@@ -1620,7 +1610,7 @@ torch::Tensor group_pooled_fwd_direct(
                           emb_rows.options().dtype(out_dtype));
   int64_t total = batch * n_tables * dim;
   if (total == 0) return out;
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   const float* wptr =
       weights.defined() && weights.numel() ? weights.data_ptr<float>()
                                            : nullptr;
@@ -1718,7 +1708,7 @@ torch::Tensor group_pooled_bwd_seg(
     TORCH_CHECK(row_ids.numel() == order.numel() &&
                     row_coeff.numel() == batch * n_tables,
                 "group_pooled_bwd_seg: row_ids/row_coeff size mismatch");
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   zero_fill(grad_unique.data_ptr<float>(), m * dim, stream);
   if (order.numel() == 0) return grad_unique;
   const float* wptr =
@@ -1760,7 +1750,7 @@ void apply_sgd(torch::Tensor w, torch::Tensor slots, torch::Tensor grad,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_sgd<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), slots.data_ptr<int32_t>(), grad.data_ptr<float>(),
       m, dim, (float)lr);
@@ -1771,7 +1761,7 @@ void apply_adagrad(torch::Tensor w, torch::Tensor accum, torch::Tensor slots,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_adagrad<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), accum.data_ptr<float>(), slots.data_ptr<int32_t>(),
       grad.data_ptr<float>(), m, dim, (float)lr, (float)epsilon);
@@ -1785,7 +1775,7 @@ void apply_adagrad_decay(torch::Tensor w, torch::Tensor accum,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_adagrad_decay<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), accum.data_ptr<float>(),
       period_slab.data_ptr<float>(), slots.data_ptr<int32_t>(),
@@ -1802,7 +1792,7 @@ void apply_adam(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_adam<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), mom.data_ptr<float>(), vel.data_ptr<float>(),
       slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr_t,
@@ -1816,7 +1806,7 @@ void apply_adam_dev(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_adam_dev<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), mom.data_ptr<float>(), vel.data_ptr<float>(),
       slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr,
@@ -1825,7 +1815,7 @@ void apply_adam_dev(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
 }
 
 void update_powers(torch::Tensor powers, double beta1, double beta2) {
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_update_powers<<<1, 64, 0, stream>>>(powers.data_ptr<float>(),
                                         (float)beta1, (float)beta2);
 }
@@ -1837,7 +1827,7 @@ void apply_adamw(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_adamw<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), mom.data_ptr<float>(), vel.data_ptr<float>(),
       slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr_t,
@@ -1851,7 +1841,7 @@ void apply_rmsprop(torch::Tensor w, torch::Tensor vel, torch::Tensor slots,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_rmsprop<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), vel.data_ptr<float>(), slots.data_ptr<int32_t>(),
       grad.data_ptr<float>(), m, dim, (float)lr, (float)beta2,
@@ -1864,7 +1854,7 @@ void apply_ftrl(torch::Tensor w, torch::Tensor n, torch::Tensor z,
   int m = slots.numel();
   if (m == 0) return;
   int dim = w.size(1);
-  auto stream = current_stream();
+  auto stream = current_hip_stream();
   k_apply_ftrl<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
       w.data_ptr<float>(), n.data_ptr<float>(), z.data_ptr<float>(),
       slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr,

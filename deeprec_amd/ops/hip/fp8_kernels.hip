@@ -20,37 +20,15 @@
 // exact in fp32 — the only quantization error is the e4m3 rounding of
 // the inputs, which tests bound against a torch fp32 reference.
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
+#include "hip_common.h"
+
 #include <hip/hip_fp8.h>
 
-#include <cstdint>
-
 namespace py = pybind11;
-
-static inline hipStream_t fp8_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
 
 namespace {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
-
-__device__ __forceinline__ float fp8_bf2f(short u) {
-  union { unsigned int i; float f; } cv;
-  cv.i = ((unsigned int)(unsigned short)u) << 16;
-  return cv.f;
-}
-
-__device__ __forceinline__ short fp8_f2bf(float f) {
-  union { float f; unsigned int i; } cv;
-  cv.f = f;
-  unsigned int lsb = (cv.i >> 16) & 1;
-  cv.i += 0x7fff + lsb;
-  return (short)(cv.i >> 16);
-}
 
 __device__ __forceinline__ uint8_t f32_to_e4m3(float v) {
   // explicit clamp so the kernel and the torch reference agree on the
@@ -75,7 +53,7 @@ __global__ void k_quant_rows_e4m3(const float* __restrict__ in_f,
     const int64_t base = row * d;
     float am = 0.0f;
     for (int i = threadIdx.x; i < d; i += blockDim.x) {
-      float v = in_f ? in_f[base + i] : fp8_bf2f(in_b[base + i]);
+      float v = in_f ? in_f[base + i] : bf2f_u16(in_b[base + i]);
       am = fmaxf(am, fabsf(v));
     }
     red[threadIdx.x] = am;
@@ -91,7 +69,7 @@ __global__ void k_quant_rows_e4m3(const float* __restrict__ in_f,
     // bit-identical to the torch reference (a 1-ulp fp32 difference at
     // an e4m3 rounding tie moves the byte by a whole e4m3 ulp)
     for (int i = threadIdx.x; i < d; i += blockDim.x) {
-      float v = in_f ? in_f[base + i] : fp8_bf2f(in_b[base + i]);
+      float v = in_f ? in_f[base + i] : bf2f_u16(in_b[base + i]);
       q[base + i] = f32_to_e4m3(v / s);
     }
     if (threadIdx.x == 0) scale[row] = s;
@@ -170,7 +148,7 @@ __global__ void k_linear_fwd_fp8(const uint8_t* __restrict__ A,
       float v = acc[t][i] * sa[cm] * swv + bv;
       if (act == 1 && v < 0.0f) v = 0.0f;
       else if (act == 2) v = 1.0f / (1.0f + __expf(-v));
-      C[(int64_t)cm * N + cn] = fp8_f2bf(v);
+      C[(int64_t)cm * N + cn] = f2bf_u16(v);
     }
   }
 }
@@ -196,7 +174,7 @@ std::tuple<torch::Tensor, torch::Tensor> quant_rows_e4m3(torch::Tensor x) {
   const short* pb = nullptr;
   if (x.scalar_type() == torch::kFloat32) pf = x.data_ptr<float>();
   else pb = reinterpret_cast<const short*>(x.data_ptr<at::BFloat16>());
-  k_quant_rows_e4m3<<<blocks, 256, 0, fp8_stream()>>>(
+  k_quant_rows_e4m3<<<blocks, 256, 0, current_hip_stream()>>>(
       pf, pb, n, d, q.data_ptr<uint8_t>(), s.data_ptr<float>());
   return {q, s};
 }
@@ -220,7 +198,7 @@ torch::Tensor linear_fwd_fp8(torch::Tensor qx, torch::Tensor sx,
     bp = bias->data_ptr<float>();
   }
   const int mtiles = (M + 63) / 64, ntiles = (N + 63) / 64;
-  k_linear_fwd_fp8<<<mtiles * ntiles, 256, 0, fp8_stream()>>>(
+  k_linear_fwd_fp8<<<mtiles * ntiles, 256, 0, current_hip_stream()>>>(
       qx.data_ptr<uint8_t>(), sx.data_ptr<float>(),
       qw.data_ptr<uint8_t>(), sw.data_ptr<float>(), bp, M, N, K, (int)act,
       reinterpret_cast<short*>(C.data_ptr<at::BFloat16>()));

@@ -23,31 +23,9 @@
 // AUGRU (attention factor a): h' = (1-a) h + a ((1-z) n + z h).
 // Constraints: H <= 32, 3H <= 96 (DIEN uses H=32).
 
-#include <torch/extension.h>
-#include <ATen/hip/HIPContext.h>
-#include <hip/hip_runtime.h>
-#include <hip/hip_bf16.h>
-
-#include <cstdint>
-
-static inline hipStream_t gru_stream() {
-  return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
-}
+#include "hip_common.h"
 
 namespace {
-
-__device__ __forceinline__ float gbf2f(short u) {
-  union { unsigned int i; float f; } cv;
-  cv.i = ((unsigned int)(unsigned short)u) << 16;
-  return cv.f;
-}
-__device__ __forceinline__ short gf2bf(float f) {
-  union { float f; unsigned int i; } cv;
-  cv.f = f;
-  unsigned int lsb = (cv.i >> 16) & 1;
-  cv.i += 0x7fff + lsb;
-  return (short)(cv.i >> 16);
-}
 
 constexpr int MAXH = 32;
 constexpr int MAX3H = 96;
@@ -82,7 +60,7 @@ __global__ void k_gru_fwd(const short* __restrict__ X3,   // [B,T,3H] bf16
         if (g < H3) {
           float s = bh[g];
           for (int k = 0; k < H; ++k)
-            s += gbf2f(u_l[g][k]) * h_l[wave][k];
+            s += bf2f_u16(u_l[g][k]) * h_l[wave][k];
           a_l[wave][g] = s;
         }
       }
@@ -91,9 +69,9 @@ __global__ void k_gru_fwd(const short* __restrict__ X3,   // [B,T,3H] bf16
     // phase 2: gates + state update (lanes 0..H-1)
     if (active && lane < H) {
       int64_t xbase = ((int64_t)b * T + t) * H3;
-      float xr = gbf2f(X3[xbase + lane]);
-      float xz = gbf2f(X3[xbase + H + lane]);
-      float xn = gbf2f(X3[xbase + 2 * H + lane]);
+      float xr = bf2f_u16(X3[xbase + lane]);
+      float xz = bf2f_u16(X3[xbase + H + lane]);
+      float xn = bf2f_u16(X3[xbase + 2 * H + lane]);
       float r = 1.0f / (1.0f + __expf(-(xr + a_l[wave][lane])));
       float z = 1.0f / (1.0f + __expf(-(xz + a_l[wave][H + lane])));
       float n = tanhf(xn + r * a_l[wave][2 * H + lane]);
@@ -108,9 +86,9 @@ __global__ void k_gru_fwd(const short* __restrict__ X3,   // [B,T,3H] bf16
       h_l[wave][lane] = h;
       int64_t obase = ((int64_t)b * T + t) * H;
       h_out[obase + lane] = h;
-      gates[xbase + lane] = gf2bf(r);
-      gates[xbase + H + lane] = gf2bf(z);
-      gates[xbase + 2 * H + lane] = gf2bf(n);
+      gates[xbase + lane] = f2bf_u16(r);
+      gates[xbase + H + lane] = f2bf_u16(z);
+      gates[xbase + 2 * H + lane] = f2bf_u16(n);
     }
     __syncthreads();
   }
@@ -153,7 +131,7 @@ __global__ void k_gru_bwd(
       int g = 2 * H + lane;
       float s = bh[g];
       for (int k = 0; k < H; ++k)
-        s += gbf2f(u_l[g][k]) * h_l[wave][k];
+        s += bf2f_u16(u_l[g][k]) * h_l[wave][k];
       pn_l[wave][lane] = s;
     }
     __syncthreads();
@@ -161,9 +139,9 @@ __global__ void k_gru_bwd(
     float dh_prev_direct = 0.0f;
     if (active && lane < H) {
       int64_t gbase = ((int64_t)b * T + t) * H3;
-      float r = gbf2f(gates[gbase + lane]);
-      float z = gbf2f(gates[gbase + H + lane]);
-      float n = gbf2f(gates[gbase + 2 * H + lane]);
+      float r = bf2f_u16(gates[gbase + lane]);
+      float z = bf2f_u16(gates[gbase + H + lane]);
+      float n = bf2f_u16(gates[gbase + 2 * H + lane]);
       float h_prev = h_l[wave][lane];
       float dht = dh_carry + dh_out[((int64_t)b * T + t) * H + lane];
       float eff = 1.0f, da_part = 0.0f;
@@ -180,13 +158,13 @@ __global__ void k_gru_bwd(
       float dpz = dz * z * (1.0f - z);
       float dr = dpn * pn_l[wave][lane];
       float dpr = dr * r * (1.0f - r);
-      dpre_x[gbase + lane] = gf2bf(dpr);
-      dpre_x[gbase + H + lane] = gf2bf(dpz);
-      dpre_x[gbase + 2 * H + lane] = gf2bf(dpn);
+      dpre_x[gbase + lane] = f2bf_u16(dpr);
+      dpre_x[gbase + H + lane] = f2bf_u16(dpz);
+      dpre_x[gbase + 2 * H + lane] = f2bf_u16(dpn);
       float dpn_h = dpn * r;
-      dpre_h[gbase + lane] = gf2bf(dpr);
-      dpre_h[gbase + H + lane] = gf2bf(dpz);
-      dpre_h[gbase + 2 * H + lane] = gf2bf(dpn_h);
+      dpre_h[gbase + lane] = f2bf_u16(dpr);
+      dpre_h[gbase + H + lane] = f2bf_u16(dpz);
+      dpre_h[gbase + 2 * H + lane] = f2bf_u16(dpn_h);
       dp_l[wave][lane] = dpr;
       dp_l[wave][H + lane] = dpz;
       dp_l[wave][2 * H + lane] = dpn_h;
@@ -197,7 +175,7 @@ __global__ void k_gru_bwd(
     if (active && lane < H) {
       float s = dh_prev_direct;
       for (int g = 0; g < H3; ++g)
-        s += dp_l[wave][g] * gbf2f(u_l[g][lane]);
+        s += dp_l[wave][g] * bf2f_u16(u_l[g][lane]);
       dh_carry = s;
       if constexpr (AUGRU) {
         if (lane == 0) {
@@ -226,7 +204,7 @@ std::tuple<torch::Tensor, torch::Tensor> gru_fwd(
   auto gates = torch::empty({B, T, 3 * H},
                             x3.options().dtype(torch::kBFloat16));
   int blocks = (int)((B + 3) / 4);
-  auto stream = gru_stream();
+  auto stream = current_hip_stream();
   const bool augru = alpha.defined() && alpha.numel() > 0;
   auto* x3p = reinterpret_cast<const short*>(x3.data_ptr<at::BFloat16>());
   auto* up = reinterpret_cast<const short*>(u_bf16.data_ptr<at::BFloat16>());
@@ -257,7 +235,7 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> gru_bwd(
                                    h_out.options().dtype(torch::kFloat32))
                     : torch::Tensor();
   int blocks = (int)((B + 3) / 4);
-  auto stream = gru_stream();
+  auto stream = current_hip_stream();
   auto* gp = reinterpret_cast<const short*>(gates.data_ptr<at::BFloat16>());
   auto* up = reinterpret_cast<const short*>(u_bf16.data_ptr<at::BFloat16>());
   auto* dxp = reinterpret_cast<short*>(dpre_x.data_ptr<at::BFloat16>());

@@ -55,7 +55,7 @@ def main():
     args = p.parse_args()
     ext = require_extension()
     dev = torch.device("cuda")
-    names = ("fwd0", "fwd1", "dx", "dw16", "dw64", "dw64t")
+    names = ("fwd0", "fwd1", "dx", "dw16", "dw64t")
     print(f"{'M':>6} {'N':>4} {'K':>4} | "
           + " ".join(f"{n:>12}" for n in names) + "  us (spread)")
     tot = [0.0] * len(names)
@@ -68,7 +68,6 @@ def main():
                lambda: ext.linear_fwd(A, W, b, 1, 1),
                lambda: ext.linear_dx(G, W),
                lambda: ext.linear_dw(G, A, True, 0),
-               lambda: ext.linear_dw(G, A, True, 1),
                lambda: ext.linear_dw(G, A, True, 2))
         res = [time_fn(fn, args.iters, args.loops) for fn in fns]
         print(f"{M:>6} {N:>4} {K:>4} | "
