@@ -41,7 +41,10 @@ class _FusedMHA(torch.autograd.Function):
 
 def _torch_mha(q, k, v, key_pad, n_heads, scale):
     """CPU/reference attention: softmax(QK^T * scale) V with key padding
-    (pad rows attend nothing; padded queries still produce outputs)."""
+    (pad rows attend nothing; padded queries still produce outputs). A
+    sample whose keys are ALL padded returns zeros and passes no gradient,
+    like the kernel and masked_softmax_pool (softmax over an all-masked
+    row would give the uniform mean of V instead)."""
     b, t, d = q.shape
     dh = d // n_heads
     qs = q.view(b, t, n_heads, dh).transpose(1, 2).float()
@@ -50,6 +53,8 @@ def _torch_mha(q, k, v, key_pad, n_heads, scale):
     scores = torch.matmul(qs, ks.transpose(-1, -2)) * scale
     scores = scores.masked_fill(key_pad[:, None, None, :], -1e30)
     p = torch.softmax(scores, dim=-1)
+    live = (~key_pad).any(dim=1)[:, None, None, None]
+    p = torch.where(live, p, torch.zeros_like(p))
     out = torch.matmul(p, vs)
     return out.transpose(1, 2).reshape(b, t, d).to(q.dtype)
 
@@ -209,8 +214,12 @@ def masked_softmax_pool(scores: torch.Tensor, seq: torch.Tensor,
         return _MaskedSoftmaxPool.apply(
             scores.float().contiguous(), seq.float().contiguous(),
             mask.to(torch.uint8).contiguous())
-    mf = mask.to(scores.dtype)
-    s = scores.float() - scores.float().amax(dim=1, keepdim=True)
-    e = torch.exp(s) * mf
+    valid = mask.bool()
+    # the max runs over the valid positions only, like the kernel's: a
+    # large score in a masked slot must not flush the valid ones to zero
+    s = scores.float().masked_fill(~valid, torch.finfo(torch.float32).min)
+    s = torch.where(valid, s - s.amax(dim=1, keepdim=True),
+                    torch.zeros_like(s))
+    e = torch.exp(s) * valid.to(s.dtype)
     w = e / (e.sum(dim=1, keepdim=True) + 1e-20)
     return (w.unsqueeze(2) * seq.float()).sum(1)

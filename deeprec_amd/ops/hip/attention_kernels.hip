@@ -17,6 +17,8 @@
 
 #include "hip_common.h"
 
+#include <c10/hip/HIPException.h>
+
 namespace {
 
 constexpr int kMaxDh = 32;  // head dim cap (template dispatch below)
@@ -392,37 +394,113 @@ static short* att_bf_ptr_mut(torch::Tensor& t) {
   return reinterpret_cast<short*>(t.data_ptr<at::BFloat16>());
 }
 
+// Host-side admission for the attention launches. Both directions keep
+// the whole sample in dynamic LDS, so the request grows with T*D; it is
+// checked against the device's own per-block limit (queried, not assumed)
+// before anything is launched, and the launch status is checked after, so
+// a refused launch raises instead of handing back uninitialised tensors.
+static size_t mha_lds_request(int64_t T, int64_t D, int64_t H, bool bwd) {
+  const size_t tile = (size_t)T * D * sizeof(short);  // one [T, D] operand
+  return bwd ? 4 * tile + (size_t)T * H * sizeof(float) : 2 * tile;
+}
+
+static int64_t mha_lds_limit_for(int device) {
+  int v = 0;
+  C10_HIP_CHECK(hipDeviceGetAttribute(
+      &v, hipDeviceAttributeMaxSharedMemoryPerBlock, device));
+  return v;
+}
+
+int64_t mha_lds_limit() {
+  int device = 0;
+  C10_HIP_CHECK(hipGetDevice(&device));
+  return mha_lds_limit_for(device);
+}
+
+int64_t mha_lds_bytes(int64_t T, int64_t D, int64_t H, bool bwd) {
+  return (int64_t)mha_lds_request(T, D, H, bwd);
+}
+
+static void check_mha_operand(const torch::Tensor& t, const torch::Tensor& q,
+                              const char* name, bool need_contiguous) {
+  TORCH_CHECK(t.is_cuda() && t.get_device() == q.get_device(), "mha: ", name,
+              " must be on the device of q");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, "mha: ", name,
+              " must be bf16");
+  TORCH_CHECK(t.sizes() == q.sizes(), "mha: ", name, " must have q's shape");
+  TORCH_CHECK(!need_contiguous || t.is_contiguous(), "mha: ", name,
+              " must be contiguous");
+}
+
+// shapes, dtypes and the LDS request shared by both directions
+static void check_mha(const torch::Tensor& q, const torch::Tensor& k,
+                      const torch::Tensor& v, const torch::Tensor& key_pad,
+                      int64_t n_heads, bool bwd) {
+  TORCH_CHECK(q.dim() == 3, "mha: q must be [B, T, D]");
+  check_mha_operand(q, q, "q", true);
+  check_mha_operand(k, q, "k", true);
+  check_mha_operand(v, q, "v", true);
+  const int64_t B = q.size(0), T = q.size(1), D = q.size(2);
+  TORCH_CHECK(key_pad.is_cuda() && key_pad.get_device() == q.get_device(),
+              "mha: key_pad must be on the device of q");
+  TORCH_CHECK(key_pad.scalar_type() == torch::kUInt8,
+              "mha: key_pad must be uint8");
+  TORCH_CHECK(key_pad.is_contiguous() && key_pad.dim() == 2
+                  && key_pad.size(0) == B && key_pad.size(1) == T,
+              "mha: key_pad must be contiguous [B, T]");
+  TORCH_CHECK(n_heads >= 1 && D % n_heads == 0 && D / n_heads <= kMaxDh,
+              "head dim too large");
+  const int64_t dh = D / n_heads;
+  TORCH_CHECK(dh == 4 || dh == 8 || dh == 16 || dh == 32,
+              "head dim must be 4/8/16/32");
+  TORCH_CHECK(T * n_heads <= 1024,
+              "sequence too long for the per-sample block");
+  const int64_t need = (int64_t)mha_lds_request(T, D, n_heads, bwd);
+  const int64_t limit = mha_lds_limit_for(q.get_device());
+  TORCH_CHECK(need <= limit, "mha_", bwd ? "bwd" : "fwd", ": T=", T, " D=", D,
+              " H=", n_heads, " needs ", need,
+              " bytes of LDS per block, the device allows ", limit);
+}
+
+// A request above the default dynamic-LDS size has to be announced for
+// the kernel; below it this is skipped, so the common shapes pay nothing.
+template <typename K>
+static void mha_allow_lds(K kernel, size_t lds) {
+  if (lds > 48 * 1024) {
+    C10_HIP_CHECK(hipFuncSetAttribute(
+        reinterpret_cast<const void*>(kernel),
+        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  }
+}
+
 std::tuple<torch::Tensor, torch::Tensor> mha_fwd(torch::Tensor q,
                                                  torch::Tensor k,
                                                  torch::Tensor v,
                                                  torch::Tensor key_pad,
                                                  int64_t n_heads,
                                                  double scale) {
-  TORCH_CHECK(q.scalar_type() == torch::kBFloat16 && q.is_contiguous());
-  TORCH_CHECK(key_pad.scalar_type() == torch::kUInt8);
+  check_mha(q, k, v, key_pad, n_heads, false);
   int B = q.size(0), T = q.size(1), D = q.size(2);
   int H = (int)n_heads;
-  TORCH_CHECK(D % H == 0 && D / H <= kMaxDh, "head dim too large");
-  TORCH_CHECK(T * H <= 1024, "sequence too long for the per-sample block");
   auto out = torch::empty_like(q);
   auto stats = torch::empty({B, (int64_t)H, (int64_t)T, 2},
                             q.options().dtype(torch::kFloat32));
-  if (B == 0) return {out, stats};
-  size_t lds = 2 * (size_t)T * D * sizeof(short);
+  if (B == 0 || T == 0) return {out, stats};
+  size_t lds = mha_lds_request(T, D, H, false);
   int threads = std::min(1024, ((T * H + 63) / 64) * 64);
   const int dh = D / H;
-  TORCH_CHECK(dh == 4 || dh == 8 || dh == 16 || dh == 32,
-              "head dim must be 4/8/16/32");
 #define MHA_FWD(DHV) \
+  mha_allow_lds(k_mha_fwd<DHV>, lds); \
   k_mha_fwd<DHV><<<B, threads, lds, current_hip_stream()>>>( \
       att_bf_ptr(q), att_bf_ptr(k), att_bf_ptr(v), \
       key_pad.data_ptr<uint8_t>(), B, T, D, H, (float)scale, \
       att_bf_ptr_mut(out), stats.data_ptr<float>())
-  if (dh == 4) MHA_FWD(4);
-  else if (dh == 8) MHA_FWD(8);
-  else if (dh == 16) MHA_FWD(16);
-  else MHA_FWD(32);
+  if (dh == 4) { MHA_FWD(4); }
+  else if (dh == 8) { MHA_FWD(8); }
+  else if (dh == 16) { MHA_FWD(16); }
+  else { MHA_FWD(32); }
 #undef MHA_FWD
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {out, stats};
 }
 
@@ -430,27 +508,37 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> mha_bwd(
     torch::Tensor dout, torch::Tensor q, torch::Tensor k, torch::Tensor v,
     torch::Tensor key_pad, torch::Tensor stats, int64_t n_heads,
     double scale) {
+  check_mha(q, k, v, key_pad, n_heads, true);
+  check_mha_operand(dout, q, "dout", false);
   int B = q.size(0), T = q.size(1), D = q.size(2);
   int H = (int)n_heads;
+  TORCH_CHECK(stats.is_cuda() && stats.get_device() == q.get_device()
+                  && stats.scalar_type() == torch::kFloat32
+                  && stats.is_contiguous() && stats.dim() == 4
+                  && stats.size(0) == B && stats.size(1) == H
+                  && stats.size(2) == T && stats.size(3) == 2,
+              "mha_bwd: stats must be contiguous fp32 [B, H, T, 2]");
   auto dq = torch::empty_like(q);
   auto dk = torch::empty_like(k);
   auto dv = torch::empty_like(v);
-  if (B == 0) return {dq, dk, dv};
-  size_t lds = 4 * (size_t)T * D * sizeof(short)
-               + (size_t)T * H * sizeof(float);
+  if (B == 0 || T == 0) return {dq, dk, dv};
+  size_t lds = mha_lds_request(T, D, H, true);
   int threads = std::min(1024, ((T * H + 63) / 64) * 64);
   const int dh = D / H;
+  auto dc = dout.contiguous();
 #define MHA_BWD(DHV) \
+  mha_allow_lds(k_mha_bwd<DHV>, lds); \
   k_mha_bwd<DHV><<<B, threads, lds, current_hip_stream()>>>( \
-      att_bf_ptr(dout.contiguous()), att_bf_ptr(q), att_bf_ptr(k), \
+      att_bf_ptr(dc), att_bf_ptr(q), att_bf_ptr(k), \
       att_bf_ptr(v), key_pad.data_ptr<uint8_t>(), stats.data_ptr<float>(), \
       B, T, D, H, (float)scale, att_bf_ptr_mut(dq), att_bf_ptr_mut(dk), \
       att_bf_ptr_mut(dv))
-  if (dh == 4) MHA_BWD(4);
-  else if (dh == 8) MHA_BWD(8);
-  else if (dh == 16) MHA_BWD(16);
-  else MHA_BWD(32);
+  if (dh == 4) { MHA_BWD(4); }
+  else if (dh == 8) { MHA_BWD(8); }
+  else if (dh == 16) { MHA_BWD(16); }
+  else { MHA_BWD(32); }
 #undef MHA_BWD
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dq, dk, dv};
 }
 
@@ -460,10 +548,12 @@ torch::Tensor din_feat_fwd(torch::Tensor seq, torch::Tensor tgt) {
   auto out = torch::empty({(int64_t)B * T, 4 * (int64_t)D},
                           seq.options().dtype(torch::kBFloat16));
   int64_t total = (int64_t)B * T * D;
+  if (total == 0) return out;  // an empty grid is a launch error
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
   k_din_feat_fwd<<<blocks, 256, 0, current_hip_stream()>>>(
       seq.data_ptr<float>(), tgt.data_ptr<float>(), B, T, D,
       att_bf_ptr_mut(out));
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return out;
 }
 
@@ -475,14 +565,21 @@ std::tuple<torch::Tensor, torch::Tensor> din_feat_bwd(torch::Tensor g,
   auto dtgt = torch::empty_like(tgt);
   auto gc = g.contiguous();
   int64_t total = (int64_t)B * T * D;
+  if ((int64_t)B * D == 0) return {dseq, dtgt};
+  if (total == 0) {  // T = 0: nothing to sum, dtgt is all zero
+    dtgt.zero_();
+    return {dseq, dtgt};
+  }
   int blocks = (int)std::min<int64_t>((total + 255) / 256, 8192);
   k_din_feat_bwd_ds<<<blocks, 256, 0, current_hip_stream()>>>(
       att_bf_ptr(gc), tgt.data_ptr<float>(), B, T, D,
       dseq.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   int blocks2 = (int)std::min<int64_t>(((int64_t)B * D + 255) / 256, 8192);
   k_din_feat_bwd_dt<<<blocks2, 256, 0, current_hip_stream()>>>(
       att_bf_ptr(gc), seq.data_ptr<float>(), B, T, D,
       dtgt.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dseq, dtgt};
 }
 
@@ -503,6 +600,7 @@ std::tuple<torch::Tensor, torch::Tensor> msm_pool_fwd(torch::Tensor scores,
       scores.data_ptr<float>(), seq.data_ptr<float>(),
       mask.data_ptr<uint8_t>(), B, T, D, w.data_ptr<float>(),
       out.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {out, w};
 }
 
@@ -520,12 +618,16 @@ std::tuple<torch::Tensor, torch::Tensor> msm_pool_bwd(torch::Tensor dout,
       dc.data_ptr<float>(), seq.data_ptr<float>(), w.data_ptr<float>(),
       mask.data_ptr<uint8_t>(), B, T, D, dscores.data_ptr<float>(),
       dseq.data_ptr<float>());
+  C10_HIP_KERNEL_LAUNCH_CHECK();
   return {dscores, dseq};
 }
 
 void register_attention(pybind11::module_& mod) {
   mod.def("mha_fwd", &mha_fwd);
   mod.def("mha_bwd", &mha_bwd);
+  mod.def("mha_lds_limit", &mha_lds_limit);
+  mod.def("mha_lds_bytes", &mha_lds_bytes, pybind11::arg("T"),
+          pybind11::arg("D"), pybind11::arg("H"), pybind11::arg("bwd"));
   mod.def("din_feat_fwd", &din_feat_fwd);
   mod.def("din_feat_bwd", &din_feat_bwd);
   mod.def("msm_pool_fwd", &msm_pool_fwd);
