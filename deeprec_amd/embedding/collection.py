@@ -22,9 +22,69 @@ from deeprec_amd.embedding.options import EmbeddingVariableOption
 from deeprec_amd.embedding.ragged import RaggedIds
 from deeprec_amd.embedding.variable import get_global_step
 from deeprec_amd.ops import functional as F
+from deeprec_amd.ops.common import COMBINER_ID, KEY_BITS, DedupResult
 
-KEY_BITS = 48
-_COMBINER_ID = {"sum": 0, "mean": 1, "sqrtn": 2}
+
+def unique_and_probe(storage, keys, train: bool, graph_mode: bool = False,
+                     allow_dedup: bool = True) -> DedupResult:
+    """unique + single hash probe. GPU training uses the fused hash dedup
+    (no sorts) while the storage prefers it; everything else is
+    torch.unique + the probe, with rank=None. A storage that can dedup has
+    `prefers_dedup` (and with it `dedup_lookup`, `observe_uniq_ratio`);
+    one that cannot simply lacks it."""
+    if graph_mode and train:
+        return storage.dedup_lookup_capture(keys)
+    prefers_dedup = getattr(storage, "prefers_dedup", None)
+    if train and allow_dedup and prefers_dedup is not None \
+            and prefers_dedup():
+        return storage.dedup_lookup(keys, get_global_step())
+    uniq, inverse, counts = torch.unique(
+        keys, return_inverse=True, return_counts=True)
+    slots = storage.lookup_or_create(uniq, counts, get_global_step(),
+                                     train=train)
+    if prefers_dedup is not None:
+        storage.observe_uniq_ratio(uniq.numel(), keys.numel())
+    return DedupResult(uniq, inverse.to(torch.int32), counts, slots, None,
+                       None)
+
+
+def prep_backward(storage, inverse, counts, rank=None):
+    """CSR over unique keys: `order` lists the occurrences sorted by
+    unique row, which is what the occurrence-balanced backward walks.
+    `rank` is the DedupResult.rank that came with this `inverse`."""
+    m = counts.numel()
+    c32 = counts.to(torch.int32)
+    bounds = torch.zeros(m + 1, dtype=torch.int32, device=inverse.device)
+    bounds[1:] = c32.cumsum(0)
+    if inverse.device.type != "cuda":
+        order = torch.argsort(inverse.long()).to(torch.int32)
+    elif rank is not None:
+        # pass C already recorded each occurrence's rank within its key,
+        # so order is a direct scatter (no atomic-cursor pass over nnz)
+        order = storage.ext.csr_scatter(inverse, rank, bounds,
+                                        storage.error_flag)
+    else:  # torch.unique (sort) path
+        order = storage.ext.csr_order(inverse, bounds, m)
+    return order, bounds
+
+
+def row_coeffs(comb, offsets, row_ids, weights):
+    """Combiner coefficient per pooled row. `comb` holds the combiner id
+    of each row (or one id, broadcast); `weights` is fp32 or None."""
+    lengths = (offsets[1:] - offsets[:-1]).float()
+    if weights is None:
+        wsum = lengths
+        wsq = lengths
+    else:
+        wsum = torch.zeros_like(lengths)
+        wsum.index_add_(0, row_ids.long(), weights)
+        wsq = torch.zeros_like(lengths)
+        wsq.index_add_(0, row_ids.long(), weights * weights)
+    denom = torch.where(comb == 2, wsq.sqrt(), wsum)
+    coeff = torch.where(comb == 0, torch.ones_like(denom),
+                        1.0 / denom.clamp(min=1e-12))
+    # empty rows get 0 under every combiner; no occurrence reads it
+    return torch.where(lengths > 0, coeff, torch.zeros_like(coeff))
 
 
 class EmbeddingCollection:
@@ -60,7 +120,7 @@ class EmbeddingCollection:
         self.storage.key_bits = KEY_BITS
         self.storage.dvd_per_table = dvd
         self._combiner_ids = torch.tensor(
-            [_COMBINER_ID[c] for c in self.combiners], dtype=torch.int32,
+            [COMBINER_ID[c] for c in self.combiners], dtype=torch.int32,
             device=self.device)
         self._anchor = torch.zeros((), device=self.device,
                                    requires_grad=trainable)
@@ -121,21 +181,8 @@ class EmbeddingCollection:
 
     def _row_coeffs(self, offsets_cat, row_ids_cat, weights_cat, batch):
         """[N*B] combiner coefficient per pooled row."""
-        lengths = (offsets_cat[1:] - offsets_cat[:-1]).float()
-        comb = self._combiner_ids.repeat_interleave(batch)  # [N*B]
-        if weights_cat is None:
-            wsum = lengths
-            wsq = lengths
-        else:
-            wsum = torch.zeros_like(lengths)
-            wsum.index_add_(0, row_ids_cat.long(), weights_cat)
-            wsq = torch.zeros_like(lengths)
-            wsq.index_add_(0, row_ids_cat.long(), weights_cat * weights_cat)
-        denom = torch.where(comb == 2, wsq.sqrt(), wsum)
-        coeff = torch.where(comb == 0, torch.ones_like(denom),
-                            1.0 / denom.clamp(min=1e-12))
-        coeff = torch.where(lengths > 0, coeff, torch.zeros_like(coeff))
-        return coeff
+        return row_coeffs(self._combiner_ids.repeat_interleave(batch),
+                          offsets_cat, row_ids_cat, weights_cat)
 
     def lookup(self, sp_list: Sequence[RaggedIds], out_dtype=None,
                train: bool = True) -> torch.Tensor:
@@ -144,64 +191,47 @@ class EmbeddingCollection:
         batch, values_cat, offsets_cat, row_ids_cat, weights_cat = \
             self._concat_inputs(sp_list)
         train = train and self.trainable
-        uniq, inverse, counts, slots = self._dedup_and_probe(
-            values_cat, train)
-        if train and self._record_sparse_ids:
-            self._recorded_ids.append(uniq.detach())
+        d = self._dedup_and_probe(values_cat, train)
         if not train:
-            return self._forward(uniq, slots, inverse, offsets_cat,
+            return self._forward(d.uniq, d.slots, d.inverse, offsets_cat,
                                  weights_cat, batch, out_dtype)
-        order, bounds = self._prep_backward(inverse, counts)
+        order, bounds = self._prep_backward(d.inverse, d.counts, d.rank)
         row_coeff = self._row_coeffs(offsets_cat, row_ids_cat, weights_cat,
                                      batch)
         return _CollectionLookup.apply(
-            self._anchor, self, uniq, slots, inverse, offsets_cat,
+            self._anchor, self, d.uniq, d.slots, d.inverse, offsets_cat,
             row_ids_cat, order, bounds, row_coeff, weights_cat, batch,
             out_dtype, False)
 
-    def _dedup_and_probe(self, values_cat, train):
-        """unique + single hash probe. GPU training uses the fused hash
-        dedup (no sorts); other paths use torch.unique + the probe."""
-        # a rank buffer from an earlier un-consumed dedup must never pair
-        # with this call's inverse (the sort path orders keys differently)
-        self.storage._last_rank = None
-        if self.graph_mode and train:
-            return self.storage.dedup_lookup_capture(values_cat)
-        if (train and hasattr(self.storage, "dedup_lookup")
-                and self.storage.prefers_dedup()):
-            return self.storage.dedup_lookup(values_cat, get_global_step())
-        uniq, inverse, counts = torch.unique(
-            values_cat, return_inverse=True, return_counts=True)
-        slots = self.storage.lookup_or_create(
-            uniq, counts, get_global_step(), train=train)
-        if hasattr(self.storage, "observe_uniq_ratio"):
-            self.storage.observe_uniq_ratio(uniq.numel(),
-                                            values_cat.numel())
-        return uniq, inverse.to(torch.int32), counts, slots
+    def _dedup_and_probe(self, values_cat, train) -> DedupResult:
+        d = unique_and_probe(self.storage, values_cat, train,
+                             self.graph_mode)
+        if train and self._record_sparse_ids:
+            self._recorded_ids.append(d.uniq.detach())
+        return d
 
-    def _prep_backward(self, inverse, counts):
-        """CSR over unique keys: `order` lists the occurrences sorted by
-        unique row, which is what the occurrence-balanced backward
-        walks."""
-        m = counts.numel()
-        dev = self.device
-        c32 = counts.to(torch.int32)
-        bounds = torch.zeros(m + 1, dtype=torch.int32, device=dev)
-        bounds[1:] = c32.cumsum(0)
-        if self.device.type != "cuda":
-            order = torch.argsort(inverse.long()).to(torch.int32)
-            return order, bounds
-        # sort-free CSR build; when the fused dedup ran, pass C already
-        # recorded each occurrence's rank within its key, so order is a
-        # direct scatter (no second atomic-cursor pass over nnz)
-        rank = getattr(self.storage, "_last_rank", None)
-        self.storage._last_rank = None
-        if rank is not None and rank.numel() == inverse.numel():
-            order = self.storage.ext.csr_scatter(
-                inverse, rank, bounds, self.storage.error_flag)
-        else:  # torch.unique (sort) path
-            order = self.storage.ext.csr_order(inverse, bounds, m)
-        return order, bounds
+    def _prep_backward(self, inverse, counts, rank=None):
+        return prep_backward(self.storage, inverse, counts, rank)
+
+    def matrix_inputs(self, ids: torch.Tensor):
+        """(values_cat, offsets, row_ids, row_coeff) for ids [batch,
+        n_tables], one id per table per sample. Everything but the
+        tagged keys is cached per batch size."""
+        batch, n = ids.shape
+        assert n == self.n_tables
+        cache = self._matrix_cache.get(batch)
+        if cache is None:
+            dev = self.device
+            nb = n * batch
+            cache = (
+                torch.arange(nb + 1, dtype=torch.int32, device=dev),
+                torch.arange(nb, dtype=torch.int32, device=dev),
+                torch.ones(nb, device=dev),
+                (torch.arange(n, dtype=torch.int64, device=dev)
+                 << KEY_BITS).repeat_interleave(batch))
+            self._matrix_cache[batch] = cache
+        offsets, row_ids, row_coeff, tags = cache
+        return ids.t().reshape(-1) + tags, offsets, row_ids, row_coeff
 
     def lookup_matrix(self, ids: torch.Tensor, out_dtype=None,
                       train: bool = True) -> torch.Tensor:
@@ -210,35 +240,17 @@ class EmbeddingCollection:
         combiner coeffs, table tags) is cached per batch size, so a step
         costs: 1 transpose+add, 1 unique, the probe, the fused fwd/bwd and
         the apply."""
-        batch, n = ids.shape
-        assert n == self.n_tables
-        cache = self._matrix_cache.get(batch)
-        if cache is None:
-            dev = self.device
-            nb = n * batch
-            cache = {
-                "offsets": torch.arange(nb + 1, dtype=torch.int32,
-                                        device=dev),
-                "row_ids": torch.arange(nb, dtype=torch.int32, device=dev),
-                "row_coeff": torch.ones(nb, device=dev),
-                "tags": (torch.arange(n, dtype=torch.int64, device=dev)
-                         << KEY_BITS).repeat_interleave(batch),
-            }
-            self._matrix_cache[batch] = cache
-        values_cat = ids.t().reshape(-1) + cache["tags"]
+        batch = ids.shape[0]
+        values_cat, offsets, row_ids, row_coeff = self.matrix_inputs(ids)
         train = train and self.trainable
-        uniq, inverse, counts, slots = self._dedup_and_probe(
-            values_cat, train)
-        if train and self._record_sparse_ids:
-            self._recorded_ids.append(uniq.detach())
+        d = self._dedup_and_probe(values_cat, train)
         if not train:
-            return self._forward(uniq, slots, inverse, cache["offsets"],
-                                 None, batch, out_dtype)
-        order, bounds = self._prep_backward(inverse, counts)
+            return self._forward(d.uniq, d.slots, d.inverse, offsets, None,
+                                 batch, out_dtype)
+        order, bounds = self._prep_backward(d.inverse, d.counts, d.rank)
         return _CollectionLookup.apply(
-            self._anchor, self, uniq, slots, inverse, cache["offsets"],
-            cache["row_ids"], order, bounds, cache["row_coeff"], None,
-            batch, out_dtype, True)
+            self._anchor, self, d.uniq, d.slots, d.inverse, offsets,
+            row_ids, order, bounds, row_coeff, None, batch, out_dtype, True)
 
     def _forward(self, uniq, slots, inverse, offsets_cat, weights_cat, batch,
                  out_dtype, emb_override=None):

@@ -16,13 +16,17 @@ fusion (ops/kv_variable_ops.cc:636).
 """
 from __future__ import annotations
 
+import os
 from typing import List, Sequence
 
 import torch
 
+from deeprec_amd.embedding.collection import (prep_backward, row_coeffs,
+                                              unique_and_probe)
 from deeprec_amd.embedding.ragged import RaggedIds
 from deeprec_amd.embedding.variable import EmbeddingVariable
 from deeprec_amd.ops import functional as F
+from deeprec_amd.ops.common import COMBINER_ID
 
 
 class _PooledLookup(torch.autograd.Function):
@@ -66,38 +70,20 @@ class _PooledLookup(torch.autograd.Function):
         return (torch.zeros_like(ctx.ev._anchor),) + (None,) * 10
 
 
-_COMBINER_ID = {"sum": 0, "mean": 1, "sqrtn": 2}
-
-
 def _chunked_ev_backward(ev, grad_out, inverse, offsets, row_ids, counts,
                          combiner, weights):
-    ext = ev.storage.ext
-    dev = grad_out.device
+    """The collection's segmented backward with n_tables=1."""
+    st = ev.storage
     m = counts.numel()
-    c32 = counts.to(torch.int32)
-    bounds = torch.zeros(m + 1, dtype=torch.int32, device=dev)
-    bounds[1:] = c32.cumsum(0)
-    order = ext.csr_order(inverse, bounds, m)
-    # per-row combiner coefficients
-    lengths = (offsets[1:] - offsets[:-1]).float()
-    if combiner == "sum":
-        row_coeff = torch.ones_like(lengths)
-    else:
-        if weights is None:
-            denom = lengths if combiner == "mean" else lengths.sqrt()
-        else:
-            acc = torch.zeros_like(lengths)
-            w = (weights.float() if combiner == "mean"
-                 else weights.float() ** 2)
-            acc.index_add_(0, row_ids.long(), w)
-            denom = acc if combiner == "mean" else acc.sqrt()
-        row_coeff = torch.where(lengths > 0,
-                                1.0 / denom.clamp(min=1e-12),
-                                torch.zeros_like(lengths))
-    return ext.group_pooled_bwd_seg(
+    weights = weights.float() if weights is not None else None
+    order, _ = prep_backward(st, inverse, counts)
+    comb = torch.full((1,), COMBINER_ID[combiner], dtype=torch.int32,
+                      device=grad_out.device)
+    row_coeff = row_coeffs(comb, offsets, row_ids, weights)
+    return st.ext.group_pooled_bwd_seg(
         grad_out.contiguous(), order, inverse.to(torch.int32),
         row_ids.to(torch.int32),
-        weights.float() if weights is not None else torch.Tensor(),
+        weights if weights is not None else torch.Tensor(),
         row_coeff, m, offsets.numel() - 1, 1, ev.dim, False, 0)
 
 
@@ -132,24 +118,13 @@ def embedding_lookup_sparse(ev: EmbeddingVariable, sp_ids: RaggedIds,
         # never admitted, never trained, zeros in the pooled output
         # (reference: invalid-key semantics of get_embedding_variable)
         sp_ids = _drop_positions(sp_ids, sp_ids.values != inv)
-    import os
-    use_dedup = (train and ev.trainable
-                 and hasattr(ev.storage, "dedup_lookup")
-                 and ev.storage.prefers_dedup()
-                 and not os.environ.get("DEEPREC_AMD_DISABLE_DEDUP"))
-    if use_dedup:
-        # fused hash dedup (sort-free) on the GPU training path
-        from deeprec_amd.embedding.variable import get_global_step
-        uniq, inverse, counts, slots = ev.storage.dedup_lookup(
-            sp_ids.values, get_global_step())
-        if ev._record_sparse_ids:
-            ev._recorded_ids.append(uniq.detach())
-    else:
-        uniq, inverse, counts = torch.unique(
-            sp_ids.values, return_inverse=True, return_counts=True)
-        slots = ev.lookup_or_create(uniq, counts, train=train)
-        if hasattr(ev.storage, "observe_uniq_ratio"):
-            ev.storage.observe_uniq_ratio(uniq.numel(), sp_ids.nnz)
+    # fused hash dedup (sort-free) on the GPU training path
+    uniq, inverse, counts, slots, _rank, _m = unique_and_probe(
+        ev.storage, sp_ids.values, train,
+        allow_dedup=ev.trainable
+        and not os.environ.get("DEEPREC_AMD_DISABLE_DEDUP"))
+    if train and ev._record_sparse_ids:
+        ev._recorded_ids.append(uniq.detach())
     row_ids = sp_ids.row_ids()
     if not (train and ev.trainable):
         emb = ev.storage.gather(uniq, slots)
@@ -190,17 +165,11 @@ def group_embedding_lookup_sparse(evs: Sequence[EmbeddingVariable],
                                   combiners=None, out_dtype=None,
                                   train: bool = True) -> List[torch.Tensor]:
     """N lookups in one call (reference: GroupEmbeddingVarLookup,
-    ops/kv_variable_ops.cc:404). The HIP backend batches the probe +
-    gather/pool of all tables into grouped kernel launches; the generic
-    path simply loops."""
+    ops/kv_variable_ops.cc:404). Loops over the tables; the fused
+    multi-table path is EmbeddingCollection."""
     if combiners is None:
         combiners = ["mean"] * len(evs)
     if len(evs) != len(sp_ids_list) or len(evs) != len(combiners):
         raise ValueError("group_embedding_lookup_sparse: length mismatch")
-    dev = evs[0].device if evs else torch.device("cpu")
-    all_plain = all(isinstance(e, EmbeddingVariable) for e in evs)
-    if dev.type == "cuda" and train and all_plain:
-        from deeprec_amd.ops.hip_backend import group_pooled_lookup
-        return group_pooled_lookup(evs, sp_ids_list, combiners, out_dtype)
     return [embedding_lookup_sparse(ev, sp, c, out_dtype, train)
             for ev, sp, c in zip(evs, sp_ids_list, combiners)]

@@ -32,7 +32,8 @@ import os
 import torch
 
 from deeprec_amd.embedding.options import EmbeddingVariableOption
-from deeprec_amd.ops.hip_backend import _COMBINER_ID, HbmStorage
+from deeprec_amd.ops.common import COMBINER_ID
+from deeprec_amd.ops.hip_backend import HbmStorage
 
 _GROW = 2
 
@@ -198,9 +199,9 @@ class HbmDramStorage(HbmStorage):
 
     def dedup_lookup(self, values_cat, step):
         prev = self._watermark()
-        uniq, inverse, counts, slots = super().dedup_lookup(values_cat, step)
-        self._init_cold_rows(uniq, slots, prev)
-        return uniq, inverse, counts, slots
+        res = super().dedup_lookup(values_cat, step)
+        self._init_cold_rows(res.uniq, res.slots, prev)
+        return res
 
     def _default_rows_cpu(self, keys):
         if self.key_bits > 0:
@@ -249,7 +250,7 @@ class HbmDramStorage(HbmStorage):
                       weights, out_dtype):
         emb = self.materialize(keys, slots)
         # reuse the direct-rows fused pooling (single-table = 1 "table")
-        comb = torch.tensor([_COMBINER_ID[combiner]], dtype=torch.int32,
+        comb = torch.tensor([COMBINER_ID[combiner]], dtype=torch.int32,
                             device=self.device)
         return self.ext.group_pooled_fwd_direct(
             emb, keys, inverse.to(torch.int32), offsets.to(torch.int32),

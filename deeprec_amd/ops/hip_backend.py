@@ -19,8 +19,8 @@ from deeprec_amd.embedding.options import (
     L2WeightEvict,
 )
 from deeprec_amd.ops.build_ext import require_extension
+from deeprec_amd.ops.common import COMBINER_ID, DedupResult
 
-_COMBINER_ID = {"sum": 0, "mean": 1, "sqrtn": 2}
 _LOAD_FACTOR = 0.6
 
 
@@ -283,45 +283,40 @@ class HbmStorage:
             self.default_values, self.dvd_per_table, self.key_bits,
             self._init_limit(), self.filter_freq, self.error_flag)
 
-    def dedup_lookup_capture(self, values_cat: torch.Tensor):
+    def dedup_lookup_capture(self, values_cat: torch.Tensor) -> DedupResult:
         """Sync-free, fixed-shape dedup+probe for hipGraph capture: all
         outputs are nnz-padded; the true unique count lives in a device
-        counter consumed by the padded pass B (tail slots = -1)."""
+        counter (m_dev) consumed by the padded pass B (tail slots = -1)."""
         self.ext.bump_epoch(self._epoch_dev, self._step_dev)
         uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
             values_cat, self._epoch_dev)
-        self._last_m_dev = m_counter
         # pass C first: its exact per-batch counts feed pass B's single
         # per-unique freq update (pass A is claim-only — hot keys no
         # longer serialize per-occurrence atomics)
         inverse, counts, rank = self._dedup_count(occ_entry,
                                                   values_cat.numel())
-        self._last_rank = rank  # consumed by collection._prep_backward
         slots = self._dedup_admit(centry_buf, uniq_buf, counts,
                                   m_dev=m_counter)
-        return uniq_buf, inverse, counts, slots
+        return DedupResult(uniq_buf, inverse, counts, slots, rank, m_counter)
 
-    def dedup_only_capture(self, values_cat: torch.Tensor):
+    def dedup_only_capture(self, values_cat: torch.Tensor) -> DedupResult:
         """Requester-side dedup for the padded sharded exchange: claim-only
         pass A + pass C against the local table (NO admission, NO
         freq/version writes — those happen once, on the owner). Non-owned
         keys become slot-less entries here (the table doubles as the dedup
         structure); they are cheap (~32 B) and never exported.
 
-        Returns (uniq_buf [nnz] padded, inverse i32 [nnz], counts i32
-        [nnz] padded, m_counter device scalar). Capture-safe: no host
-        syncs, all shapes static."""
+        uniq and counts are nnz-padded, slots is None, m_dev holds the
+        unique count. Capture-safe: no host syncs, all shapes static."""
         self.ext.bump_epoch(self._epoch_dev, self._step_dev)
         uniq_buf, _centry, occ_entry, m_counter = self._dedup_claim(
             values_cat, self._epoch_dev)
-        self._last_m_dev = m_counter
         inverse, counts, rank = self._dedup_count(occ_entry,
                                                   values_cat.numel())
-        self._last_rank = rank
-        return uniq_buf, inverse, counts, m_counter
+        return DedupResult(uniq_buf, inverse, counts, None, rank, m_counter)
 
     def dedup_lookup_capture_owner(self, recv_keys: torch.Tensor,
-                                   recv_cnt: torch.Tensor):
+                                   recv_cnt: torch.Tensor) -> DedupResult:
         """Owner-side dedup+admission for the padded sharded exchange:
         full pipeline (A, C, B) over the w*cap received keys, except the
         freq bump uses the SUMMED true per-batch counts carried on the
@@ -341,7 +336,8 @@ class HbmStorage:
         cnt_sum = self.ext.cnt_sum_pad(inverse, recv_cnt, nnz)
         slots = self._dedup_admit(centry_buf, uniq_buf, cnt_sum,
                                   m_dev=m_counter)
-        return uniq_buf, inverse, slots
+        return DedupResult(uniq_buf, inverse, cnt_sum, slots, None,
+                           m_counter)
 
     def prefers_dedup(self) -> bool:
         # hash dedup is O(nnz) probes; torch.unique is a full radix/merge
@@ -357,10 +353,12 @@ class HbmStorage:
         self._uniq_ratio = (r if self._uniq_ratio is None
                             else 0.7 * self._uniq_ratio + 0.3 * r)
 
-    def dedup_lookup(self, values_cat: torch.Tensor, step: int):
+    def dedup_lookup(self, values_cat: torch.Tensor,
+                     step: int) -> DedupResult:
         """Fused unique+probe for a training step: raw (duplicated) keys in,
-        (uniq, inverse i32, counts i32, slots i32) out. One host sync (the
-        unique count) — the same sync torch.unique pays — and no sorts."""
+        exact-size uniq / inverse i32 / counts i32 / slots i32 out. One
+        host sync (the unique count) — the same sync torch.unique pays —
+        and no sorts."""
         nnz = values_cat.numel()
         self._ensure_capacity(nnz)
         self._epoch += 1
@@ -378,9 +376,8 @@ class HbmStorage:
         uniq = uniq_buf[:m]
         # pass C first: exact counts feed pass B's per-unique freq update
         inverse, counts, rank = self._dedup_count(occ_entry, m)
-        self._last_rank = rank  # consumed by collection._prep_backward
         slots = self._dedup_admit(centry_buf[:m], uniq, counts, step=step)
-        return uniq, inverse, counts, slots
+        return DedupResult(uniq, inverse, counts, slots, rank, None)
 
     def _use_no_permission(self) -> bool:
         return (self.filter_freq > 0 and
@@ -403,7 +400,7 @@ class HbmStorage:
             self.values, self.default_values, keys, slots,
             inverse.to(torch.int32), offsets.to(torch.int32),
             weights.float() if weights is not None else torch.Tensor(),
-            _COMBINER_ID[combiner], self._no_permission_value(),
+            COMBINER_ID[combiner], self._no_permission_value(),
             self._use_no_permission(), out_dtype or torch.float32)
 
     def pooled_grad(self, grad_out, inverse, offsets, row_ids, m, combiner,
@@ -412,7 +409,7 @@ class HbmStorage:
             grad_out.contiguous(), inverse.to(torch.int32),
             offsets.to(torch.int32),
             weights.float() if weights is not None else torch.Tensor(),
-            m, _COMBINER_ID[combiner])
+            m, COMBINER_ID[combiner])
 
     # ---------------- shrink / export / import ----------------
     def shrink(self, step: int) -> int:
@@ -637,10 +634,3 @@ def sparse_apply(name: str, storage: HbmStorage, slots, grad, hyper: dict):
     else:
         raise ValueError(f"unknown sparse optimizer {name!r}")
 
-
-def group_pooled_lookup(evs, sp_ids_list, combiners, out_dtype):
-    """Grouped lookup fast path — per-table loop for now; the fused
-    multi-table kernel lands with the EmbeddingCollection."""
-    from deeprec_amd.embedding.lookup import embedding_lookup_sparse
-    return [embedding_lookup_sparse(ev, sp, c, out_dtype)
-            for ev, sp, c in zip(evs, sp_ids_list, combiners)]

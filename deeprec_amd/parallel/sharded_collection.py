@@ -12,14 +12,15 @@ shape that drives all 7 point-to-point links concurrently.
 """
 from __future__ import annotations
 
-from typing import Optional, Sequence
+from typing import NamedTuple, Optional, Sequence
 
 import torch
 
-from deeprec_amd.embedding.collection import KEY_BITS, EmbeddingCollection
+from deeprec_amd.embedding.collection import EmbeddingCollection
 from deeprec_amd.embedding.options import EmbeddingVariableOption
 from deeprec_amd.embedding.ragged import RaggedIds
 from deeprec_amd.embedding.variable import get_global_step
+from deeprec_amd.ops.common import KEY_BITS, PAD_KEY
 from deeprec_amd.parallel import comm
 
 
@@ -113,26 +114,10 @@ class ShardedEmbeddingCollection:
     # ---- lookups ----
     def lookup_matrix(self, ids: torch.Tensor, out_dtype=None,
                       train: bool = True) -> torch.Tensor:
-        batch, n = ids.shape
-        assert n == self.n_tables
-        coll = self.local
-        cache = coll._matrix_cache.get(batch)
-        if cache is None:
-            dev = coll.device
-            nb = n * batch
-            cache = {
-                "offsets": torch.arange(nb + 1, dtype=torch.int32,
-                                        device=dev),
-                "row_ids": torch.arange(nb, dtype=torch.int32, device=dev),
-                "row_coeff": torch.ones(nb, device=dev),
-                "tags": (torch.arange(n, dtype=torch.int64, device=dev)
-                         << KEY_BITS).repeat_interleave(batch),
-            }
-            coll._matrix_cache[batch] = cache
-        values_cat = ids.t().reshape(-1) + cache["tags"]
-        return self._lookup_cat(values_cat, cache["offsets"],
-                                cache["row_ids"], cache["row_coeff"], None,
-                                batch, out_dtype, train)
+        values_cat, offsets, row_ids, row_coeff = \
+            self.local.matrix_inputs(ids)
+        return self._lookup_cat(values_cat, offsets, row_ids, row_coeff,
+                                None, ids.shape[0], out_dtype, train)
 
     def lookup(self, sp_list: Sequence[RaggedIds], out_dtype=None,
                train: bool = True) -> torch.Tensor:
@@ -201,9 +186,6 @@ class ShardedEmbeddingCollection:
         self.static_mode(pad_cap)
 
 
-PAD_KEY = (1 << 63) - 1  # == ext.PAD_KEY (engine wire-padding sentinel)
-
-
 def _route_pad_cpu(uniq, counts, world, cap, key_bits):
     """CPU/gloo reference of the k_route_pad kernel: scatter unique keys
     into per-peer blocks of `cap` rows, pad with PAD_KEY. Returns
@@ -232,6 +214,87 @@ def _route_pad_cpu(uniq, counts, world, cap, key_bits):
     return send_keys, send_cnt, route_pos
 
 
+class _PaddedExchange(NamedTuple):
+    """What one padded exchange leaves for its backward."""
+    inverse: torch.Tensor      # occurrence -> requester unique row
+    order: torch.Tensor        # requester CSR over those rows ...
+    bounds: torch.Tensor       # ... [m_req + 1]
+    route_pos: torch.Tensor    # requester unique row -> wire row
+    m_dev: Optional[torch.Tensor]  # device unique count (GPU engine only:
+    #                                its rows are nnz-padded)
+    own_inv: torch.Tensor      # received wire row -> owned unique row
+    own_keys: torch.Tensor     # owned unique keys and their slots: what
+    own_slots: torch.Tensor    # the optimizer applies the gradient to
+
+
+def _padded_lookup_gpu(sev, values_cat):
+    """Engine side of the padded exchange; every shape is static.
+    -> (exchange state, rows [w*cap, D], their keys, occurrence -> row)"""
+    coll, st = sev.local, sev.local.storage
+    w, cap = sev.world, sev._pad_cap
+    splits = [cap] * w
+    # requester dedup (no admission) and routing into per-peer blocks
+    req = st.dedup_only_capture(values_cat)
+    send_keys, send_cnt, route_pos = st.ext.route_pad(
+        req.uniq, req.counts, req.m_dev, w, cap, KEY_BITS, st.error_flag)
+    order, bounds = coll._prep_backward(req.inverse, req.counts, req.rank)
+    recv_keys = comm.all_to_all_single(send_keys, splits, splits)
+    recv_cnt = comm.all_to_all_single(send_cnt, splits, splits)
+    # owner dedup + admission, then one row per received key
+    own = st.dedup_lookup_capture_owner(recv_keys, recv_cnt)
+    slots_elem = st.ext.slots_gather_pad(own.inverse, own.slots)
+    reply = st.ext.ev_gather(
+        st.values, st.default_values, recv_keys, slots_elem,
+        st._no_permission_value(), st._use_no_permission(),
+        sev.comm_dtype or torch.float32)
+    emb_rows = comm.all_to_all_single(reply, splits, splits).float()
+    ex = _PaddedExchange(req.inverse, order, bounds, route_pos, req.m_dev,
+                         own.inverse, own.uniq, own.slots)
+    return ex, emb_rows, recv_keys, st.ext.compose_i32(req.inverse,
+                                                       route_pos)
+
+
+def _padded_lookup_cpu(sev, values_cat):
+    """CPU/gloo reference of _padded_lookup_gpu: the same wire protocol
+    on torch ops, with exact-size (unpadded) unique sets."""
+    coll, st = sev.local, sev.local.storage
+    w, cap = sev.world, sev._pad_cap
+    splits = [cap] * w
+    # requester dedup and routing into per-peer blocks
+    uniq, inv_t, counts = torch.unique(
+        values_cat, return_inverse=True, return_counts=True)
+    inverse = inv_t.to(torch.int32)
+    order, bounds = coll._prep_backward(inverse, counts)
+    send_keys, send_cnt, route_pos = _route_pad_cpu(uniq, counts, w, cap,
+                                                    KEY_BITS)
+    recv_keys = comm.all_to_all_single(send_keys, splits, splits)
+    recv_cnt = comm.all_to_all_single(send_cnt, splits, splits)
+    # owner dedup + admission; PAD_KEY is the largest int64, so it sorts
+    # last and the owned keys are a prefix of uniq2
+    uniq2, inv2 = torch.unique(recv_keys, return_inverse=True)
+    cnt2 = torch.zeros(uniq2.numel(), dtype=torch.int64)
+    cnt2.index_add_(0, inv2, recv_cnt.long())
+    n_own = int((uniq2 != PAD_KEY).sum())
+    own_keys = uniq2[:n_own]
+    own_slots = st.lookup_or_create(own_keys, cnt2[:n_own],
+                                    get_global_step(), train=True)
+    # one row per received key (zeros for pads)
+    reply = torch.zeros(uniq2.numel(), coll.dim)
+    reply[:n_own] = st.gather(own_keys, own_slots)
+    reply = reply[inv2]
+    if sev.comm_dtype is not None:
+        lp = reply.to(sev.comm_dtype).contiguous()
+        emb_rows = comm.all_to_all_single(
+            lp.view(torch.int16), splits, splits) \
+            .view(sev.comm_dtype).float()
+    else:
+        emb_rows = comm.all_to_all_single(reply.contiguous(), splits,
+                                          splits)
+    ex = _PaddedExchange(inverse, order, bounds, route_pos, None, inv2,
+                         own_keys, own_slots)
+    return ex, emb_rows, uniq2, route_pos[inverse.long()].to(torch.int32)
+
+
 def _padded_sharded_lookup(sev, values_cat, offsets_cat, row_ids_cat,
                            row_coeff, weights_cat, batch, out_dtype):
     """Fixed-shape training lookup: requester dedup -> padded all-to-all
@@ -240,120 +303,56 @@ def _padded_sharded_lookup(sev, values_cat, offsets_cat, row_ids_cat,
     data, so the WHOLE sequence (RCCL collectives included) records into
     a hipGraph and replays. Eager execution uses the identical wire
     protocol (gloo/CPU runs it in tests)."""
-    coll = sev.local
-    st = coll.storage
-    w, cap = sev.world, sev._pad_cap
-    dev = coll.device
-    is_gpu = dev.type == "cuda"
-    splits = [cap] * w
-    if is_gpu:
-        uniq_buf, inverse, counts, m_dev = st.dedup_only_capture(values_cat)
-        send_keys, send_cnt, route_pos = st.ext.route_pad(
-            uniq_buf, counts, m_dev, w, cap, KEY_BITS, st.error_flag)
-        # CSR prep consumes pass C's rank before anything else overwrites
-        order, bounds = coll._prep_backward(inverse, counts)
-        m_req = values_cat.numel()
-    else:
-        uniq, inv_t, cnt_t = torch.unique(
-            values_cat, return_inverse=True, return_counts=True)
-        inverse = inv_t.to(torch.int32)
-        st._last_rank = None
-        order, bounds = coll._prep_backward(inverse, cnt_t)
-        send_keys, send_cnt, route_pos = _route_pad_cpu(
-            uniq, cnt_t, w, cap, KEY_BITS)
-        m_dev = None
-        m_req = uniq.numel()
-    recv_keys = comm.all_to_all_single(send_keys, splits, splits)
-    recv_cnt = comm.all_to_all_single(send_cnt, splits, splits)
-    if is_gpu:
-        uniq2, inv2, slots2 = st.dedup_lookup_capture_owner(recv_keys,
-                                                            recv_cnt)
-        slots_elem = st.ext.slots_gather_pad(inv2, slots2)
-        wire = sev.comm_dtype or torch.float32
-        reply = st.ext.ev_gather(
-            st.values, st.default_values, recv_keys, slots_elem,
-            st._no_permission_value(), st._use_no_permission(), wire)
-        own_valid = None
-        emb_rows = comm.all_to_all_single(reply, splits, splits).float()
-        inverse_final = st.ext.compose_i32(inverse, route_pos)
-        keys_for_kernel = recv_keys
-    else:
-        uniq2, inv2 = torch.unique(recv_keys, return_inverse=True)
-        cnt2 = torch.zeros(uniq2.numel(), dtype=torch.int64)
-        cnt2.index_add_(0, inv2, recv_cnt.long())
-        own_valid = uniq2 != PAD_KEY
-        slots_v = st.lookup_or_create(uniq2[own_valid], cnt2[own_valid],
-                                      get_global_step(), train=True)
-        emb_v = st.gather(uniq2[own_valid], slots_v)
-        reply = torch.zeros(uniq2.numel(), coll.dim)
-        reply[own_valid] = emb_v
-        reply = reply[inv2]
-        slots2 = slots_v
-        if sev.comm_dtype is not None:
-            lp = reply.to(sev.comm_dtype).contiguous()
-            emb_rows = comm.all_to_all_single(
-                lp.view(torch.int16), splits, splits) \
-                .view(sev.comm_dtype).float()
-        else:
-            emb_rows = comm.all_to_all_single(reply.contiguous(), splits,
-                                              splits)
-        inverse_final = route_pos[inverse.long()].to(torch.int32)
-        keys_for_kernel = uniq2
-    if is_gpu:
-        inverse_final = inverse_final.to(torch.int32)
+    exchange = (_padded_lookup_gpu if sev.local.device.type == "cuda"
+                else _padded_lookup_cpu)
+    ex, emb_rows, keys, inverse_final = exchange(sev, values_cat)
     return _PaddedShardedLookup.apply(
-        coll._anchor, sev, emb_rows, keys_for_kernel, inverse_final,
-        offsets_cat, row_ids_cat, order, bounds, inverse, row_coeff,
-        weights_cat, batch, out_dtype, m_req, m_dev, route_pos, inv2, slots2,
-        uniq2, own_valid)
+        sev.local._anchor, sev, ex, emb_rows, keys, inverse_final,
+        offsets_cat, row_ids_cat, row_coeff, weights_cat, batch, out_dtype)
 
 
 class _PaddedShardedLookup(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, anchor, sev, emb_rows, keys_for_kernel, inverse_final,
-                offsets_cat, row_ids_cat, order, bounds, inverse, row_coeff,
-                weights_cat, batch, out_dtype, m_req, m_dev, route_pos,
-                inv2, slots2, uniq2, own_valid):
-        out = sev.local._forward(keys_for_kernel, None, inverse_final,
-                                 offsets_cat, weights_cat, batch, out_dtype,
+    def forward(ctx, anchor, sev, ex, emb_rows, keys, inverse_final,
+                offsets_cat, row_ids_cat, row_coeff, weights_cat, batch,
+                out_dtype):
+        out = sev.local._forward(keys, None, inverse_final, offsets_cat,
+                                 weights_cat, batch, out_dtype,
                                  emb_override=emb_rows)
         ctx.sev = sev
+        ctx.ex = ex
         ctx.batch = batch
         ctx.weights_cat = weights_cat
-        ctx.m_req = m_req
-        ctx.m_dev = m_dev
-        ctx.own_valid = own_valid
-        ctx.save_for_backward(order, bounds, inverse, row_ids_cat, row_coeff,
-                              route_pos, inv2, slots2, uniq2)
+        ctx.save_for_backward(row_ids_cat, row_coeff)
         return out
 
     @staticmethod
     def backward(ctx, grad_out):
-        sev = ctx.sev
+        sev, ex = ctx.sev, ctx.ex
         coll = sev.local
         st = coll.storage
         w, cap = sev.world, sev._pad_cap
         splits = [cap] * w
-        order, bounds, inverse, row_ids_cat, row_coeff, route_pos, inv2, \
-            slots2, uniq2 = ctx.saved_tensors
-        grad_unique = coll._backward(grad_out, order, bounds, inverse,
-                                     row_ids_cat, ctx.weights_cat,
-                                     row_coeff, ctx.m_req, ctx.batch)
+        row_ids_cat, row_coeff = ctx.saved_tensors
+        grad_unique = coll._backward(grad_out, ex.order, ex.bounds,
+                                     ex.inverse, row_ids_cat,
+                                     ctx.weights_cat, row_coeff,
+                                     ex.bounds.numel() - 1, ctx.batch)
         if coll.device.type == "cuda":
-            grad_send = st.ext.rows_to_padded(grad_unique, route_pos,
-                                              ctx.m_dev, w * cap)
+            grad_send = st.ext.rows_to_padded(grad_unique, ex.route_pos,
+                                              ex.m_dev, w * cap)
             grad_recv = comm.all_to_all_single(grad_send, splits, splits)
-            grad2 = st.ext.rows_segsum_pad(grad_recv, inv2, w * cap)
-            coll.accumulate_grad(slots2, uniq2, grad2)
+            grad_own = st.ext.rows_segsum_pad(grad_recv, ex.own_inv, w * cap)
         else:
             grad_send = torch.zeros(w * cap, grad_unique.shape[1])
-            grad_send[route_pos] = grad_unique
+            grad_send[ex.route_pos] = grad_unique
             grad_recv = comm.all_to_all_single(grad_send, splits, splits)
-            grad2 = torch.zeros(uniq2.numel(), grad_recv.shape[1])
-            grad2.index_add_(0, inv2, grad_recv)
-            valid = ctx.own_valid
-            coll.accumulate_grad(slots2, uniq2[valid], grad2[valid])
-        return (torch.zeros_like(coll._anchor),) + (None,) * 20
+            n_own = ex.own_keys.numel()  # row n_own collects the pads
+            grad_own = torch.zeros(n_own + 1, grad_recv.shape[1])
+            grad_own.index_add_(0, ex.own_inv, grad_recv)
+            grad_own = grad_own[:n_own]
+        coll.accumulate_grad(ex.own_slots, ex.own_keys, grad_own)
+        return (torch.zeros_like(coll._anchor),) + (None,) * 11
 
 
 def _a2a(sev: ShardedEmbeddingCollection, tensor, in_sp, out_sp):

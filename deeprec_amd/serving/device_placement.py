@@ -25,7 +25,6 @@ class CpuOffloadStorage:
         self.key_bits = inner.key_bits
         self.dvd_per_table = inner.dvd_per_table
         self.slabs = {}
-        self._last_rank = None
 
     def lookup(self, keys):
         return self.inner.lookup(keys.cpu()).to(keys.device)
@@ -38,12 +37,6 @@ class CpuOffloadStorage:
     def gather(self, keys, slots, out_dtype=None):
         rows = self.inner.gather(keys.cpu(), slots.cpu(), out_dtype)
         return rows.to(self.out_device)
-
-    def prefers_dedup(self):
-        return False
-
-    def observe_uniq_ratio(self, m, nnz):
-        pass
 
     def frequencies(self, keys):
         return self.inner.frequencies(keys.cpu()).to(keys.device)

@@ -27,7 +27,6 @@ class RemoteKvStorage:
         self.dim = dim
         self.device = torch.device(device)
         self.default = default
-        self._last_rank = None
         self.slabs = {}
         self.key_bits = 0
         self.dvd_per_table = 1
@@ -49,12 +48,6 @@ class RemoteKvStorage:
                               self.default)
         rows = rows.to(self.device)
         return rows.to(out_dtype) if out_dtype else rows
-
-    def prefers_dedup(self):
-        return False
-
-    def observe_uniq_ratio(self, m, nnz):
-        pass
 
     def frequencies(self, keys):
         return torch.zeros(keys.numel(), dtype=torch.int64)

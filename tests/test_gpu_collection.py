@@ -175,3 +175,47 @@ def test_async_embedding_stage_gpu():
     coll.storage._check_error()
     assert torch.isfinite(loss)
     assert coll.size() > 0
+
+
+def test_interleaved_lookups_keep_their_own_rank():
+    """Two lookup_matrix forwards before either backward, the first on the
+    hash-dedup path (pass C rank -> csr_scatter), the second on the sort
+    path (no rank -> csr_order): each backward must scatter with the CSR
+    of its own lookup. Integer grads make every sum exact in fp32, so the
+    per-key gradients must EQUAL a CPU index_add_; keys are matched by
+    value because atomics decide the dedup path's unique order."""
+    batch, n_tables, dim = 64, 3, 16
+    coll = EmbeddingCollection("rank", ["a", "b", "c"], dim, device=DEV)
+    st = coll.storage
+    gen = torch.Generator().manual_seed(31)
+
+    def make(base):
+        ids = torch.randint(base, base + 50, (batch, n_tables),
+                            generator=gen)
+        for t in range(n_tables):  # one hot id per table, ~20 occurrences
+            rows = torch.randperm(batch, generator=gen)[:20]
+            ids[rows, t] = base + 7 * t
+        g = torch.randint(-4, 5, (batch, n_tables * dim), generator=gen)
+        return ids, g.to(torch.bfloat16)
+
+    (ids1, g1), (ids2, g2) = make(0), make(25)
+    assert st.prefers_dedup()
+    out1 = coll.lookup_matrix(ids1.to(DEV), out_dtype=torch.bfloat16)
+    st._uniq_ratio = 0.99  # above the dedup threshold: sort path next
+    assert not st.prefers_dedup()
+    out2 = coll.lookup_matrix(ids2.to(DEV), out_dtype=torch.bfloat16)
+    out1.backward(g1.to(DEV))
+    out2.backward(g2.to(DEV))
+    grads = coll.consume_grads()
+    assert len(grads) == 2
+    tags = (torch.arange(n_tables) << 48).repeat_interleave(batch)
+    for (slots, keys, gu), ids, g in zip(grads, (ids1, ids2), (g1, g2)):
+        occ_keys = ids.t().reshape(-1) + tags  # occurrence t * batch + b
+        occ_grad = g.float().reshape(batch, n_tables, dim) \
+            .permute(1, 0, 2).reshape(-1, dim)
+        ref_keys, inv = torch.unique(occ_keys, return_inverse=True)
+        ref = torch.zeros(ref_keys.numel(), dim).index_add_(0, inv, occ_grad)
+        order = torch.argsort(keys.cpu())
+        assert torch.equal(keys.cpu()[order], ref_keys)
+        assert torch.equal(gu.cpu().float()[order], ref)
+    st._check_error()

@@ -97,7 +97,7 @@ def test_hash_table_concurrency_stress():
             g = torch.Generator("cuda").manual_seed(step)
             keys = torch.randint(0, 5000, (4096,), device=DEV,
                                  generator=g)
-            uniq, inverse, counts, slots = st.dedup_lookup(keys, step)
+            uniq = st.dedup_lookup(keys, step).uniq
             for k in uniq.cpu().tolist():
                 oracle[k] = step
             if step % 20 == 19:
@@ -137,7 +137,8 @@ def test_dedup_insert_interleave_storm():
         g = torch.Generator("cuda").manual_seed(1000 + step)
         keys = torch.randint(0, 800, (1024,), device=DEV, generator=g)
         if step % 2 == 0:
-            uniq, inverse, counts, slots = st.dedup_lookup(keys, step)
+            d = st.dedup_lookup(keys, step)
+            uniq, counts = d.uniq, d.counts
             for k, c in zip(uniq.cpu().tolist(), counts.cpu().tolist()):
                 freq_oracle[k] = freq_oracle.get(k, 0) + c
         else:

@@ -287,7 +287,8 @@ def _default_rows(st, keys):
 def _check_dedup_step(st, keys, out, m, freq_after, padded):
     """One dedup step's outputs against torch.unique, as key -> value maps
     (the order of uniques is decided by atomics)."""
-    uniq, inverse, counts, slots = (t.cpu() for t in out)
+    uniq, inverse, counts, slots = (
+        t.cpu() for t in (out.uniq, out.inverse, out.counts, out.slots))
     keys = keys.cpu()
     ref_u, ref_c = torch.unique(keys, return_counts=True)
     assert m == ref_u.numel()
@@ -341,10 +342,11 @@ def test_dedup_entry_points_agree(composite):
             freq[k] = freq.get(k, 0) + 1
             version[k] = step
         out_a = st_a.dedup_lookup(keys, step)
-        _check_dedup_step(st_a, keys, out_a, out_a[0].numel(), freq, False)
+        assert out_a.m_dev is None  # eager: the host knows the count
+        _check_dedup_step(st_a, keys, out_a, out_a.uniq.numel(), freq,
+                          False)
         out_b = st_b.dedup_lookup_capture(keys)
-        _check_dedup_step(st_b, keys, out_b, int(st_b._last_m_dev), freq,
-                          True)
+        _check_dedup_step(st_b, keys, out_b, int(out_b.m_dev), freq, True)
     ref = {k: (freq[k], version[k]) for k in freq}
     assert _entry_map(st_a) == ref
     assert _entry_map(st_b) == ref
@@ -365,9 +367,9 @@ def test_dedup_entry_points_agree(composite):
         cnt[is_pad] = 0
         for k, c in zip(recv[~is_pad].tolist(), cnt[~is_pad].tolist()):
             total[k] = total.get(k, 0) + c
-        uniq, inverse, slots = (t.cpu() for t in
-                                st_c.dedup_lookup_capture_owner(
-                                    recv.to(DEV), cnt.to(DEV)))
+        out_c = st_c.dedup_lookup_capture_owner(recv.to(DEV), cnt.to(DEV))
+        uniq, inverse, slots = (
+            t.cpu() for t in (out_c.uniq, out_c.inverse, out_c.slots))
         assert torch.equal(inverse == -1, is_pad)
         assert torch.equal(uniq[inverse[~is_pad].long()], recv[~is_pad])
         m = len(total) + 1  # the pads dedup into one entry

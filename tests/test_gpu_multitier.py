@@ -232,7 +232,8 @@ def test_background_maintenance_no_step_spike():
     for step in range(60):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        uniq, inverse, counts, slots = st.dedup_lookup(hot_ids, step)
+        d = st.dedup_lookup(hot_ids, step)
+        uniq, slots = d.uniq, d.slots
         emb = st.gather(uniq, slots)
         st.apply_split("adagrad", slots, emb * 1e-3, dict(hyper))
         mgr.step(step)

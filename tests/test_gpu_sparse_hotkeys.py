@@ -398,11 +398,11 @@ def test_captured_dedup_backward_replays():
                          device=DEV)
 
     def step():
-        uniq, inverse, counts, slots = st.dedup_lookup_capture(s_keys)
-        order, bounds = coll._prep_backward(inverse, counts)
-        gu = coll._backward(s_grad, order, bounds, inverse, row_ids, None,
+        d = st.dedup_lookup_capture(s_keys)
+        order, bounds = coll._prep_backward(d.inverse, d.counts, d.rank)
+        gu = coll._backward(s_grad, order, bounds, d.inverse, row_ids, None,
                             row_coeff, nnz, batch, identity_rows=True)
-        return uniq, inverse, gu
+        return d.uniq, d.inverse, gu, d.m_dev
 
     k0, g0 = make_batch(0)
     s_keys.copy_(k0)
@@ -411,7 +411,7 @@ def test_captured_dedup_backward_replays():
     torch.cuda.synchronize()
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
-        uniq, inverse, gu = step()
+        uniq, inverse, gu, m_dev = step()
     torch.cuda.synchronize()
     for i in range(1, 4):
         keys, g = make_batch(i)
@@ -420,7 +420,7 @@ def test_captured_dedup_backward_replays():
         graph.replay()
         torch.cuda.synchronize()
         st._check_error()
-        m = int(st._last_m_dev)
+        m = int(m_dev)
         assert m == torch.unique(keys).numel()
         inv = inverse.cpu().long()
         assert torch.equal(uniq.cpu()[inv], keys)

@@ -164,7 +164,8 @@ def train_steps(ev, args, optimizer="adagrad", label=""):
         timed_step = step >= args.warmup
         t0 = tick()
         keys = batch_ids(args.batch, args.per_sample, args.ids, gen=gen)
-        uniq, inverse, counts, slots = ev.storage.dedup_lookup(keys, step)
+        d = ev.storage.dedup_lookup(keys, step)
+        uniq, slots = d.uniq, d.slots
         t1 = tick()
         emb = ev.storage.gather(uniq, slots)
         t2 = tick()
@@ -243,7 +244,8 @@ def phase_tier_manager(args):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         keys = batch_ids(args.batch, args.per_sample, args.ids, gen=gen)
-        uniq, inverse, counts, slots = ev.storage.dedup_lookup(keys, step)
+        d = ev.storage.dedup_lookup(keys, step)
+        uniq, slots = d.uniq, d.slots
         emb = ev.storage.gather(uniq, slots)
         hip_backend.sparse_apply("adagrad", ev.storage,
                                  slots.to(torch.int32), emb * 1e-4,
