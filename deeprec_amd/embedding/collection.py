@@ -26,14 +26,16 @@ from deeprec_amd.ops.common import COMBINER_ID, KEY_BITS, DedupResult
 
 
 def unique_and_probe(storage, keys, train: bool, graph_mode: bool = False,
-                     allow_dedup: bool = True) -> DedupResult:
+                     allow_dedup: bool = True,
+                     bump_step: bool = True) -> DedupResult:
     """unique + single hash probe. GPU training uses the fused hash dedup
     (no sorts) while the storage prefers it; everything else is
     torch.unique + the probe, with rank=None. A storage that can dedup has
     `prefers_dedup` (and with it `dedup_lookup`, `observe_uniq_ratio`);
-    one that cannot simply lacks it."""
+    one that cannot simply lacks it. bump_step=False (capture only) marks
+    a second lookup of the same storage within one step."""
     if graph_mode and train:
-        return storage.dedup_lookup_capture(keys)
+        return storage.dedup_lookup_capture(keys, bump_step=bump_step)
     prefers_dedup = getattr(storage, "prefers_dedup", None)
     if train and allow_dedup and prefers_dedup is not None \
             and prefers_dedup():

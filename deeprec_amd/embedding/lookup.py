@@ -24,9 +24,10 @@ import torch
 from deeprec_amd.embedding.collection import (prep_backward, row_coeffs,
                                               unique_and_probe)
 from deeprec_amd.embedding.ragged import RaggedIds
-from deeprec_amd.embedding.variable import EmbeddingVariable
+from deeprec_amd.embedding.variable import (EmbeddingVariable,
+                                            get_global_step)
 from deeprec_amd.ops import functional as F
-from deeprec_amd.ops.common import COMBINER_ID
+from deeprec_amd.ops.common import COMBINER_ID, PAD_KEY
 
 
 class _PooledLookup(torch.autograd.Function):
@@ -118,11 +119,15 @@ def embedding_lookup_sparse(ev: EmbeddingVariable, sp_ids: RaggedIds,
         # never admitted, never trained, zeros in the pooled output
         # (reference: invalid-key semantics of get_embedding_variable)
         sp_ids = _drop_positions(sp_ids, sp_ids.values != inv)
-    # fused hash dedup (sort-free) on the GPU training path
+    # fused hash dedup (sort-free) on the GPU training path; a graph-mode
+    # EV takes the sync-free padded form of it
+    graph_mode = bool(getattr(ev, "graph_mode", False)) and ev.trainable
     uniq, inverse, counts, slots, _rank, _m = unique_and_probe(
-        ev.storage, sp_ids.values, train,
+        ev.storage, sp_ids.values, train, graph_mode,
         allow_dedup=ev.trainable
-        and not os.environ.get("DEEPREC_AMD_DISABLE_DEDUP"))
+        and not os.environ.get("DEEPREC_AMD_DISABLE_DEDUP"),
+        bump_step=not (graph_mode and train)
+        or ev.first_lookup_of_step())
     if train and ev._record_sparse_ids:
         ev._recorded_ids.append(uniq.detach())
     row_ids = sp_ids.row_ids()
@@ -148,9 +153,104 @@ def safe_embedding_lookup_sparse(ev, sp_ids: RaggedIds, combiner="mean",
     return embedding_lookup_sparse(ev, sp_ids, combiner, out_dtype, train)
 
 
+class _PaddedSeqLookup(torch.autograd.Function):
+    """Unpooled gather over a padded id stream; the backward is the
+    segmented scatter with one table and identity rows (batch = nnz), over
+    an `order` that lists only the valid occurrences."""
+
+    @staticmethod
+    def forward(ctx, anchor, ev, uniq, slots, inverse, order, out_dtype):
+        out = ev.storage.seq_gather_pad(uniq, slots, inverse, out_dtype)
+        ctx.ev = ev
+        ctx.save_for_backward(uniq, slots, inverse, order)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        uniq, slots, inverse, order = ctx.saved_tensors
+        ev = ctx.ev
+        if grad_out.dtype not in (torch.float32, torch.bfloat16):
+            grad_out = grad_out.float()
+        none = torch.Tensor()
+        grad_unique = ev.storage.ext.group_pooled_bwd_seg(
+            grad_out.contiguous(), order, inverse, none, none, none,
+            uniq.numel(), inverse.numel(), 1, ev.dim, True, 0)
+        ev.accumulate_grad(slots, uniq, grad_unique)
+        return (torch.zeros_like(ev._anchor),) + (None,) * 6
+
+
+def masked_padded_lookup(ev, ids: torch.Tensor, pad_id: int, out_dtype=None,
+                         train: bool = True) -> torch.Tensor:
+    """Padded unpooled lookup by masking: look up `ids[ids != pad_id]` and
+    scatter the rows into zeros. Shapes depend on the data (a host sync on
+    GPU), so it cannot be captured; it runs on every storage and is the
+    reference for the static-shape path of `embedding_lookup`."""
+    flat = ids.reshape(-1)
+    mask = flat != pad_id
+    rows = embedding_lookup(ev, flat[mask], out_dtype=out_dtype, train=train)
+    emb = torch.zeros(flat.numel(), ev.dim, device=flat.device,
+                      dtype=rows.dtype)
+    emb = emb.index_put((mask.nonzero().squeeze(1),), rows)
+    return emb.reshape(*ids.shape, ev.dim)
+
+
+def _static_padded_lookup(ev, ids, pad_id, out_dtype, train):
+    """HIP-engine path of embedding_lookup(pad_id=...): every shape is a
+    function of ids.shape alone."""
+    st = ev.storage
+    flat = ids.reshape(-1).to(torch.int64)
+    n = flat.numel()
+    is_pad = flat == pad_id
+    # padding becomes the engine's reserved non-key: pass A skips it, pass
+    # C gives it inverse -1, so it never reaches the table or a counter
+    keys = torch.where(is_pad, torch.full_like(flat, PAD_KEY), flat)
+    if not (train and ev.trainable):
+        # inference: per-occurrence read-only probe, no insert
+        slots = st.lookup(keys)
+        inverse = torch.where(
+            is_pad, torch.full((n,), -1, dtype=torch.int32,
+                               device=flat.device),
+            torch.arange(n, dtype=torch.int32, device=flat.device))
+        out = st.seq_gather_pad(keys, slots, inverse, out_dtype)
+        return out.reshape(*ids.shape, ev.dim)
+    if ev.graph_mode:
+        d = st.dedup_lookup_capture(
+            keys, pad=True, bump_step=ev.first_lookup_of_step())
+    else:
+        d = st.dedup_lookup(keys, get_global_step(), pad=True)
+    if ev._record_sparse_ids:
+        if d.m_dev is not None:
+            raise RuntimeError(
+                "sparse-id recording needs the exact unique keys; "
+                "graph_mode pads them")
+        ev._recorded_ids.append(d.uniq.detach())
+    m = d.counts.numel()
+    bounds = torch.zeros(m + 1, dtype=torch.int32, device=flat.device)
+    bounds[1:] = d.counts.cumsum(0)
+    order = st.ext.csr_scatter_pad(d.inverse, d.rank, bounds, st.error_flag)
+    out = _PaddedSeqLookup.apply(ev._anchor, ev, d.uniq, d.slots, d.inverse,
+                                 order, out_dtype)
+    return out.reshape(*ids.shape, ev.dim)
+
+
 def embedding_lookup(ev: EmbeddingVariable, ids: torch.Tensor,
-                     out_dtype=None, train: bool = True) -> torch.Tensor:
-    """Unpooled lookup: ids [..., ] -> [..., dim] (sequence features)."""
+                     out_dtype=None, train: bool = True,
+                     pad_id=None) -> torch.Tensor:
+    """Unpooled lookup: ids [..., ] -> [..., dim] (sequence features).
+
+    With `pad_id`, positions equal to it are padding: zero rows in the
+    output, never admitted, never counted in frequency or version, no
+    gradient, absent from recorded sparse ids and from `ev.size()`. No
+    shape depends on how many there are. On the HIP engine this is a
+    static-shape path (padded dedup, pad-aware gather, segmented grad
+    scatter) that a graph-mode EV runs without a host sync; on CPU,
+    multi-tier and engine-less storages it is `masked_padded_lookup`."""
+    if pad_id is not None:
+        st = getattr(ev, "storage", None)
+        if (isinstance(ev, EmbeddingVariable) and ev.device.type == "cuda"
+                and hasattr(st, "ext") and not hasattr(st, "apply_split")):
+            return _static_padded_lookup(ev, ids, pad_id, out_dtype, train)
+        return masked_padded_lookup(ev, ids, pad_id, out_dtype, train)
     flat = ids.reshape(-1)
     n = flat.numel()
     offsets = torch.arange(n + 1, dtype=torch.int32, device=flat.device)

@@ -64,6 +64,8 @@ class RaggedIds:
     def row_ids(self) -> torch.Tensor:
         """int32[nnz] tensor mapping each value to its batch row."""
         lengths = (self.offsets[1:] - self.offsets[:-1]).to(torch.int64)
+        # the output size is nnz by construction; saying so spares the
+        # host sync that sizing the result from `lengths` costs on GPU
         return torch.repeat_interleave(
             torch.arange(self.batch_size, device=self.values.device,
-                         dtype=torch.int32), lengths)
+                         dtype=torch.int32), lengths, output_size=self.nnz)

@@ -95,8 +95,22 @@ class EmbeddingVariable:
         # (reference: RecordSparseIndices, incr_save_restore_ops.cc:22)
         self._recorded_ids: List[torch.Tensor] = []
         self._record_sparse_ids = False
+        # hipGraph capture (after storage.enable_graph_mode): training
+        # lookups take the sync-free, nnz-padded dedup path. Honoured by
+        # embedding_lookup(pad_id=...) and the pooled lookup.
+        self.graph_mode = False
+        self._step_bumped = False
 
     # ------------- training-step interface -------------
+    def first_lookup_of_step(self) -> bool:
+        """True for the first graph-mode training lookup since the last
+        consume_grads(). That lookup advances the storage's device step;
+        later ones of the same step advance the dedup epoch only, so
+        versions move once per step however often the EV is looked up."""
+        first = not self._step_bumped
+        self._step_bumped = True
+        return first
+
     def lookup_or_create(self, uniq_keys: torch.Tensor,
                          counts: torch.Tensor = None,
                          train: bool = True) -> torch.Tensor:
@@ -125,6 +139,7 @@ class EmbeddingVariable:
     def consume_grads(self):
         out = self._pending_grads
         self._pending_grads = []
+        self._step_bumped = False  # the optimizer step ends the step
         return out
 
     def get_slab(self, name, width=None, init_value=0.0, dtype=torch.float32):

@@ -13,17 +13,33 @@ import torch.nn as nn
 
 from deeprec_amd.data.synthetic import NUM_DENSE
 from deeprec_amd.embedding import EmbeddingVariable, embedding_lookup
+from deeprec_amd.embedding.lookup import masked_padded_lookup
 from deeprec_amd.models.common import RecModelBase, make_mlp
 
 
 class _SeqBase(RecModelBase):
-    """Adds an item EmbeddingVariable for behavior sequences + target id."""
+    """Adds an item EmbeddingVariable for behavior sequences + target id.
+
+    static_seq=False (default): the sequence is looked up by masking
+    (`flat[mask]`, data-dependent shapes, one host sync) and the target by
+    a second lookup. static_seq=True: ONE padded lookup over
+    `cat([seq_ids, target_ids[:, None]], 1)` with pad_id=0 — one dedup for
+    sequence and target, every shape static, so DIN and BST can train as a
+    captured hipGraph (GraphedTrainStep). The two modes compute the same
+    model. One difference under a counter filter: the two-lookup path can
+    admit a key between its two lookups (the sequence lookup raises its
+    frequency to the threshold, the target lookup then finds it admitted);
+    the fused lookup counts all of a step's occurrences before admission
+    is decided once, so that cannot happen. Id 0 is padding wherever it
+    appears in the fused lookup, a target id of 0 included."""
 
     def __init__(self, embedding_dim=16, item_dim=32, device="cpu",
-                 bf16=True, name="seq", num_sparse=10, **kw):
+                 bf16=True, name="seq", num_sparse=10, static_seq=False,
+                 **kw):
         super().__init__(embedding_dim, device, bf16, name=name,
                          num_sparse=num_sparse, **kw)
         self.item_dim = item_dim
+        self.static_seq = static_seq
         self.item_ev = EmbeddingVariable(f"{name}/items", item_dim,
                                          device=self.device_)
 
@@ -34,19 +50,39 @@ class _SeqBase(RecModelBase):
         """[B, T] -> [B, T, item_dim]; id 0 = padding -> zero embedding.
 
         Padding is excluded from the lookup entirely (reference
-        semantics: masked positions train nothing). Measured both ways:
-        looking up every position and masking afterwards is 7x SLOWER —
-        the ~200k-occurrence padding key dominates the unpooled lookup
-        and its CSR grad scatter even with 32-way hot-key splitting."""
-        flat = seq_ids.reshape(-1)
-        mask = flat > 0
-        emb = torch.zeros(flat.numel(), self.item_dim,
-                          device=flat.device)
-        emb = emb.index_put(
-            (mask.nonzero().squeeze(1),),
-            embedding_lookup(self.item_ev, flat[mask],
-                             train=train).float())
-        return emb.reshape(*seq_ids.shape, self.item_dim)
+        semantics: masked positions train nothing), here by masking.
+        Looking the pad id up like any key and masking afterwards was
+        measured 7x SLOWER: it becomes one ~200k-occurrence key that
+        dominates dedup, gather and the CSR grad scatter even with 32-way
+        hot-key splitting. static_seq avoids the data-dependent shapes
+        without doing that: its pads are never looked up either."""
+        return masked_padded_lookup(self.item_ev, seq_ids, 0,
+                                    train=train).float()
+
+    def seq_and_target(self, seq_ids, target_ids, train=True):
+        """-> (seq [B, T, item_dim], target [B, item_dim]), fp32."""
+        if not self.static_seq:
+            seq = self.seq_emb(seq_ids, train)
+            target = embedding_lookup(self.item_ev, target_ids,
+                                      train=train).float()
+            return seq, target
+        # sequence rows first, targets after: both results are contiguous
+        # views of the one lookup's output (id 0 is padding in both)
+        b, t = seq_ids.shape
+        both = embedding_lookup(
+            self.item_ev, torch.cat([seq_ids.reshape(-1), target_ids]),
+            train=train, pad_id=0).float()
+        return both[:b * t].reshape(b, t, self.item_dim), both[b * t:]
+
+    def seq_with_target(self, seq_ids, target_ids, train=True):
+        """-> [B, T+1, item_dim] fp32: the sequence with the target item
+        appended. static_seq looks it up in exactly this layout."""
+        if not self.static_seq:
+            seq, target = self.seq_and_target(seq_ids, target_ids, train)
+            return torch.cat([seq, target.unsqueeze(1)], 1)
+        return embedding_lookup(
+            self.item_ev, torch.cat([seq_ids, target_ids[:, None]], 1),
+            train=train, pad_id=0).float()
 
 
 class DIN(_SeqBase):
@@ -93,9 +129,7 @@ class DIN(_SeqBase):
 
     def forward(self, dense, sparse_ids, seq_ids, target_ids, train=True):
         emb = self.sparse_feats(sparse_ids, train)
-        seq = self.seq_emb(seq_ids, train)
-        target = embedding_lookup(self.item_ev, target_ids,
-                                  train=train).float()
+        seq, target = self.seq_and_target(seq_ids, target_ids, train)
         mask = seq_ids > 0
         interest = self.attend(seq, target, mask)
         x = torch.cat([dense, emb.flatten(1).float(), interest, target], 1)
@@ -149,9 +183,8 @@ class DIEN(_SeqBase):
 
     def forward(self, dense, sparse_ids, seq_ids, target_ids, train=True):
         emb = self.sparse_feats(sparse_ids, train)
-        seq = self.seq_emb(seq_ids, train)               # [B,T,Di]
-        target = embedding_lookup(self.item_ev, target_ids,
-                                  train=train).float()   # [B,Di]
+        seq, target = self.seq_and_target(seq_ids, target_ids,
+                                          train)         # [B,T,Di], [B,Di]
         mask = (seq_ids > 0).float()
         h_seq = self.gru(seq)                            # [B,T,H]
         if train and self.use_aux_loss and seq.shape[1] > 1:
@@ -223,16 +256,14 @@ class BST(_SeqBase):
 
     def forward(self, dense, sparse_ids, seq_ids, target_ids, train=True):
         emb = self.sparse_feats(sparse_ids, train)
-        seq = self.seq_emb(seq_ids, train)               # [B,T,Di]
-        target = embedding_lookup(self.item_ev, target_ids,
-                                  train=train).float()
-        x_seq = torch.cat([seq, target.unsqueeze(1)], 1)  # [B,T+1,Di]
+        x_seq = self.seq_with_target(seq_ids, target_ids,
+                                     train)              # [B,T+1,Di]
         t1 = x_seq.shape[1]
         x_seq = x_seq + self.pos[:t1]
         pad = torch.cat(
             [seq_ids <= 0,
-             torch.zeros(seq.shape[0], 1, dtype=torch.bool,
-                         device=seq.device)], 1)
+             torch.zeros(x_seq.shape[0], 1, dtype=torch.bool,
+                         device=x_seq.device)], 1)
         enc = self.encoder(x_seq, pad)
         pooled = enc.mean(1)
         x = torch.cat([dense, emb.flatten(1).float(), pooled], 1)

@@ -216,6 +216,11 @@ __global__ void k_insert_bulk(
 // the captured step, so replays keep deduplicating correctly with zero
 // host involvement).
 
+// SKIP_PAD (the padded sequence lookup): a PAD_KEY occurrence is not a key
+// at all — no probe, no claim, no table entry; it records entry -1 for
+// pass C (which skips it by key) and moves on. One body for both
+// instantiations, so the claim logic cannot drift.
+template <bool SKIP_PAD>
 __global__ void k_dedup_pass_a(
     const int64_t* __restrict__ keys, int nnz, int64_t* __restrict__ ht_keys,
     int32_t* __restrict__ ht_epoch, int32_t* __restrict__ ht_compact,
@@ -228,6 +233,12 @@ __global__ void k_dedup_pass_a(
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   for (; j < nnz; j += stride) {
     const int64_t key = keys[j];
+    if constexpr (SKIP_PAD) {
+      if (key == PAD_KEY) {
+        occ_entry[j] = -1;
+        continue;
+      }
+    }
     int64_t idx = ht_find_or_claim(ht_keys, cap_mask, key, entry_counter);
     if (idx < 0) {
       atomicExch(error_flag, 2);
@@ -602,6 +613,42 @@ __global__ void k_csr_scatter(const int32_t* __restrict__ inverse,
   }
 }
 
+// Fill n int32 words with v. A kernel for the reason k_zero_f32 gives:
+// memset nodes did not replay under hipGraph capture.
+__global__ void k_fill_i32(int32_t* __restrict__ p, int64_t n, int32_t v) {
+  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; i < n; i += stride) p[i] = v;
+}
+
+// k_csr_scatter over a padded stream: occurrences with inverse < 0 (pads)
+// are not part of any key's run and are skipped, so `order` (pre-filled
+// with -1) lists the valid occurrences in [0, n_valid) and -1 after. m is
+// the number of rows of `bounds` minus one; an inverse past it, or a
+// destination outside order, trips error 3 instead of being dereferenced.
+__global__ void k_csr_scatter_pad(const int32_t* __restrict__ inverse,
+                                  const int32_t* __restrict__ rank, int nnz,
+                                  const int32_t* __restrict__ bounds, int m,
+                                  int32_t* __restrict__ order,
+                                  int32_t* __restrict__ error_flag) {
+  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; j < nnz; j += stride) {
+    const int c = inverse[j];
+    if (c < 0) continue;
+    if (c >= m) {
+      atomicExch(error_flag, 3);
+      continue;
+    }
+    int64_t o = (int64_t)bounds[c] + rank[j];
+    if (o < 0 || o >= nnz) {
+      atomicExch(error_flag, 3);
+      continue;
+    }
+    order[o] = (int32_t)j;
+  }
+}
+
 // CSR order build: order[bounds[c] + pos++] = j (pos via per-key cursor).
 __global__ void k_csr_order(const int32_t* __restrict__ inverse, int nnz,
                             const int32_t* __restrict__ bounds,
@@ -712,6 +759,87 @@ __global__ void k_gather(
     }
     if constexpr (std::is_same_v<OutT, __hip_bfloat16>) out[t] = f2bf(v);
     else out[t] = v;
+  }
+}
+
+// Unpooled gather over a padded stream (sequence features):
+//   out[j, :] = 0                        where inverse[j] < 0 (padding)
+//   out[j, :] = row of slots[inverse[j]] otherwise, with k_gather's
+//               default-row / no-permission handling for slot < 0.
+// slots/keys may be nnz-padded (capture): only rows a valid inverse names
+// are read, and an inverse past n_uniq is treated as padding, never
+// dereferenced. Memory-bound on the [nnz, dim] write: a thread moves VEC
+// consecutive elements (VEC * sizeof(OutT) = 16 B when dim allows it) and
+// consecutive threads take consecutive chunks of a row, so a wave writes
+// whole rows back to back. VEC == 1 is the scalar path for any dim.
+template <typename OutT, int VEC>
+__global__ void k_seq_gather_pad(
+    const float* __restrict__ values, const float* __restrict__ default_values,
+    const int64_t* __restrict__ keys, const int32_t* __restrict__ slots,
+    const int32_t* __restrict__ inverse, int nnz, int n_uniq, int dim,
+    int default_value_dim, float no_permission_value, int use_no_permission,
+    OutT* __restrict__ out) {
+  const int cpr = dim / VEC;  // chunks per row
+  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  const int64_t total = (int64_t)nnz * cpr;
+  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
+  for (; t < total; t += stride) {
+    const int j = (int)(t / cpr);
+    const int d0 = (int)(t % cpr) * VEC;
+    const int u = inverse[j];
+    float v[VEC];
+#pragma unroll
+    for (int i = 0; i < VEC; ++i) v[i] = 0.0f;
+    if ((unsigned)u < (unsigned)n_uniq) {
+      const int32_t s = slots[u];
+      const float* src = nullptr;
+      if (s >= 0) {
+        src = values + (int64_t)s * dim + d0;
+      } else if (!use_no_permission) {
+        int64_t row =
+            (int64_t)((uint64_t)keys[u] % (uint64_t)default_value_dim);
+        src = default_values + row * dim + d0;
+      }
+      if (src) {
+        if constexpr (VEC % 4 == 0) {  // rows are 16-B aligned: dim % 4 == 0
+#pragma unroll
+          for (int i = 0; i < VEC; i += 4) {
+            const float4 q = *reinterpret_cast<const float4*>(src + i);
+            v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
+          }
+        } else {
+#pragma unroll
+          for (int i = 0; i < VEC; ++i) v[i] = src[i];
+        }
+      } else {
+#pragma unroll
+        for (int i = 0; i < VEC; ++i) v[i] = no_permission_value;
+      }
+    }
+    OutT* dst = out + (int64_t)j * dim + d0;
+    if constexpr (std::is_same_v<OutT, __hip_bfloat16>) {
+      if constexpr (VEC == 1) {
+        dst[0] = f2bf(v[0]);
+      } else {
+        // pack pairs of bf16 into 32-bit words: one 8- or 16-byte store
+        uint32_t w[VEC / 2];
+#pragma unroll
+        for (int i = 0; i < VEC / 2; ++i) {
+          const __hip_bfloat16 lo = f2bf(v[2 * i]), hi = f2bf(v[2 * i + 1]);
+          w[i] = (uint32_t)(*reinterpret_cast<const uint16_t*>(&lo)) |
+                 ((uint32_t)(*reinterpret_cast<const uint16_t*>(&hi)) << 16);
+        }
+        if constexpr (VEC == 8)
+          *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
+        else
+          *reinterpret_cast<uint2*>(dst) = make_uint2(w[0], w[1]);
+      }
+    } else {
+      if constexpr (VEC == 4)
+        *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
+      else
+        dst[0] = v[0];
+    }
   }
 }
 
@@ -1161,6 +1289,7 @@ static inline int n_blocks(int64_t total, int block = kBlock) {
 // Zero n 4-byte words (fp32 or int32) on the stream; see k_zero_f32 for
 // why this is not hipMemsetAsync.
 static inline void zero_fill(void* p, int64_t n, hipStream_t stream) {
+  if (n <= 0) return;  // an empty grid is a launch error
   k_zero_f32<<<n_blocks((n + 3) / 4), kBlock, 0, stream>>>(
       static_cast<float*>(p), n);
 }
@@ -1202,17 +1331,17 @@ static inline const T* opt_ptr(const c10::optional<torch::Tensor>& t) {
   return t.has_value() ? t->data_ptr<T>() : nullptr;
 }
 
-torch::Tensor ht_dedup_a(torch::Tensor keys, torch::Tensor ht_keys,
-                         torch::Tensor ht_epoch, torch::Tensor ht_compact,
-                         c10::optional<torch::Tensor> epoch_dev,
-                         int64_t epoch, torch::Tensor entry_counter,
-                         torch::Tensor m_counter, torch::Tensor uniq_keys,
-                         torch::Tensor compact_entry,
-                         torch::Tensor occ_entry, torch::Tensor error_flag) {
+template <bool SKIP_PAD>
+static torch::Tensor dedup_a_impl(
+    torch::Tensor keys, torch::Tensor ht_keys, torch::Tensor ht_epoch,
+    torch::Tensor ht_compact, c10::optional<torch::Tensor> epoch_dev,
+    int64_t epoch, torch::Tensor entry_counter, torch::Tensor m_counter,
+    torch::Tensor uniq_keys, torch::Tensor compact_entry,
+    torch::Tensor occ_entry, torch::Tensor error_flag) {
   int64_t nnz = keys.numel();
   if (nnz == 0) return m_counter;
   auto stream = current_hip_stream();
-  k_dedup_pass_a<<<n_blocks(nnz), kBlock, 0, stream>>>(
+  k_dedup_pass_a<SKIP_PAD><<<n_blocks(nnz), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
       ht_epoch.data_ptr<int32_t>(), ht_compact.data_ptr<int32_t>(),
       ht_keys.numel() - 1, opt_ptr<int32_t>(epoch_dev), (int)epoch,
@@ -1220,6 +1349,33 @@ torch::Tensor ht_dedup_a(torch::Tensor keys, torch::Tensor ht_keys,
       uniq_keys.data_ptr<int64_t>(), compact_entry.data_ptr<int64_t>(),
       occ_entry.data_ptr<int64_t>(), error_flag.data_ptr<int32_t>());
   return m_counter;
+}
+
+torch::Tensor ht_dedup_a(torch::Tensor keys, torch::Tensor ht_keys,
+                         torch::Tensor ht_epoch, torch::Tensor ht_compact,
+                         c10::optional<torch::Tensor> epoch_dev,
+                         int64_t epoch, torch::Tensor entry_counter,
+                         torch::Tensor m_counter, torch::Tensor uniq_keys,
+                         torch::Tensor compact_entry,
+                         torch::Tensor occ_entry, torch::Tensor error_flag) {
+  return dedup_a_impl<false>(keys, ht_keys, ht_epoch, ht_compact, epoch_dev,
+                             epoch, entry_counter, m_counter, uniq_keys,
+                             compact_entry, occ_entry, error_flag);
+}
+
+// Pass A of the padded sequence lookup: PAD_KEY occurrences touch nothing
+// and get occ_entry -1 (pair it with ht_dedup_c(keys=...)).
+torch::Tensor ht_dedup_a_pad(torch::Tensor keys, torch::Tensor ht_keys,
+                             torch::Tensor ht_epoch, torch::Tensor ht_compact,
+                             c10::optional<torch::Tensor> epoch_dev,
+                             int64_t epoch, torch::Tensor entry_counter,
+                             torch::Tensor m_counter, torch::Tensor uniq_keys,
+                             torch::Tensor compact_entry,
+                             torch::Tensor occ_entry,
+                             torch::Tensor error_flag) {
+  return dedup_a_impl<true>(keys, ht_keys, ht_epoch, ht_compact, epoch_dev,
+                            epoch, entry_counter, m_counter, uniq_keys,
+                            compact_entry, occ_entry, error_flag);
 }
 
 torch::Tensor ht_dedup_b(torch::Tensor compact_entry, torch::Tensor uniq_keys,
@@ -1398,6 +1554,88 @@ torch::Tensor csr_scatter(torch::Tensor inverse, torch::Tensor rank,
       bounds.data_ptr<int32_t>(), order.data_ptr<int32_t>(),
       error_flag.data_ptr<int32_t>());
   return order;
+}
+
+// order over a padded stream: positions no valid occurrence lands on hold
+// -1 (the segmented backward skips them). bounds has m + 1 rows.
+torch::Tensor csr_scatter_pad(torch::Tensor inverse, torch::Tensor rank,
+                              torch::Tensor bounds,
+                              torch::Tensor error_flag) {
+  int64_t nnz = inverse.numel();
+  auto order = torch::empty({nnz}, inverse.options());
+  if (nnz == 0) return order;
+  TORCH_CHECK(rank.numel() == nnz, "csr_scatter_pad: rank size mismatch");
+  TORCH_CHECK(bounds.numel() >= 1, "csr_scatter_pad: bounds is empty");
+  auto stream = current_hip_stream();
+  k_fill_i32<<<n_blocks(nnz), kBlock, 0, stream>>>(
+      order.data_ptr<int32_t>(), nnz, -1);
+  k_csr_scatter_pad<<<n_blocks(nnz), kBlock, 0, stream>>>(
+      inverse.data_ptr<int32_t>(), rank.data_ptr<int32_t>(), (int)nnz,
+      bounds.data_ptr<int32_t>(), (int)(bounds.numel() - 1),
+      order.data_ptr<int32_t>(), error_flag.data_ptr<int32_t>());
+  return order;
+}
+
+template <typename OutT, int VEC>
+static void launch_seq_gather_pad(
+    torch::Tensor& values, torch::Tensor& default_values, torch::Tensor& keys,
+    torch::Tensor& slots, torch::Tensor& inverse, int dim,
+    double no_permission_value, bool use_no_permission, OutT* out,
+    hipStream_t stream) {
+  int64_t nnz = inverse.numel();
+  k_seq_gather_pad<OutT, VEC>
+      <<<n_blocks(nnz * (dim / VEC)), kBlock, 0, stream>>>(
+          values.data_ptr<float>(), default_values.data_ptr<float>(),
+          keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
+          inverse.data_ptr<int32_t>(), (int)nnz, (int)slots.numel(), dim,
+          (int)default_values.size(0), (float)no_permission_value,
+          use_no_permission ? 1 : 0, out);
+}
+
+// out [nnz, dim]: zero rows where inverse < 0, else the row of
+// slots[inverse] (see k_seq_gather_pad). keys/slots may be nnz-padded.
+torch::Tensor seq_gather_pad(torch::Tensor values,
+                             torch::Tensor default_values, torch::Tensor keys,
+                             torch::Tensor slots, torch::Tensor inverse,
+                             double no_permission_value,
+                             bool use_no_permission,
+                             torch::ScalarType out_dtype) {
+  CHECK_DEV(inverse);
+  TORCH_CHECK(keys.numel() == slots.numel(),
+              "seq_gather_pad: keys/slots size mismatch");
+  TORCH_CHECK(out_dtype == torch::kFloat32 || out_dtype == torch::kBFloat16,
+              "seq_gather_pad: out dtype must be float32 or bfloat16");
+  int64_t nnz = inverse.numel();
+  int dim = values.size(1);
+  auto out = torch::empty({nnz, dim}, values.options().dtype(out_dtype));
+  if (nnz * dim == 0) return out;
+  auto stream = current_hip_stream();
+  if (out_dtype == torch::kBFloat16) {
+    auto* op = reinterpret_cast<__hip_bfloat16*>(out.data_ptr<at::BFloat16>());
+    if (dim % 8 == 0)
+      launch_seq_gather_pad<__hip_bfloat16, 8>(
+          values, default_values, keys, slots, inverse, dim,
+          no_permission_value, use_no_permission, op, stream);
+    else if (dim % 4 == 0)
+      launch_seq_gather_pad<__hip_bfloat16, 4>(
+          values, default_values, keys, slots, inverse, dim,
+          no_permission_value, use_no_permission, op, stream);
+    else
+      launch_seq_gather_pad<__hip_bfloat16, 1>(
+          values, default_values, keys, slots, inverse, dim,
+          no_permission_value, use_no_permission, op, stream);
+  } else {
+    auto* op = out.data_ptr<float>();
+    if (dim % 4 == 0)
+      launch_seq_gather_pad<float, 4>(
+          values, default_values, keys, slots, inverse, dim,
+          no_permission_value, use_no_permission, op, stream);
+    else
+      launch_seq_gather_pad<float, 1>(
+          values, default_values, keys, slots, inverse, dim,
+          no_permission_value, use_no_permission, op, stream);
+  }
+  return out;
 }
 
 torch::Tensor csr_order(torch::Tensor inverse, torch::Tensor bounds,
@@ -1873,6 +2111,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_fp8(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
+  mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);
   mod.def("ht_dedup_b", &ht_dedup_b);
   mod.def("bump_epoch", &bump_epoch);
   mod.def("bump_epoch_only", &bump_epoch_only);
@@ -1887,6 +2126,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("ht_dedup_c", &ht_dedup_c);
   mod.def("csr_order", &csr_order);
   mod.def("csr_scatter", &csr_scatter);
+  mod.def("csr_scatter_pad", &csr_scatter_pad);
+  mod.def("seq_gather_pad", &seq_gather_pad);
   mod.def("ht_insert_bulk", &ht_insert_bulk);
   mod.def("ht_lookup", &ht_lookup);
   mod.def("ht_export", &ht_export);

@@ -247,10 +247,11 @@ class HbmStorage:
                                       dtype=torch.int64, device=self.device)
 
     # ---------------- fused hash dedup: the three passes ----------------
-    def _dedup_claim(self, keys: torch.Tensor, epoch_dev=None):
+    def _dedup_claim(self, keys: torch.Tensor, epoch_dev=None, pad=False):
         """Pass A: allocate the step's buffers, then find-or-insert every
         occurrence and claim a compact index per unique key. The epoch is
         the device scalar when given (capture), else the host counter.
+        With pad, PAD_KEY occurrences touch nothing (occ_entry -1).
         Returns (uniq_buf, centry_buf, occ_entry, m_counter); the first
         three are nnz-padded, m_counter is the device unique count."""
         nnz = keys.numel()
@@ -258,10 +259,10 @@ class HbmStorage:
         centry_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
         occ_entry = torch.empty(nnz, dtype=torch.int64, device=self.device)
         m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
-        self.ext.ht_dedup_a(keys, self.ht_keys, self.ht_epoch,
-                            self.ht_compact, epoch_dev, self._epoch,
-                            self.entry_counter, m_counter, uniq_buf,
-                            centry_buf, occ_entry, self.error_flag)
+        pass_a = self.ext.ht_dedup_a_pad if pad else self.ext.ht_dedup_a
+        pass_a(keys, self.ht_keys, self.ht_epoch, self.ht_compact,
+               epoch_dev, self._epoch, self.entry_counter, m_counter,
+               uniq_buf, centry_buf, occ_entry, self.error_flag)
         return uniq_buf, centry_buf, occ_entry, m_counter
 
     def _dedup_count(self, occ_entry: torch.Tensor, m: int, pad_keys=None):
@@ -283,18 +284,27 @@ class HbmStorage:
             self.default_values, self.dvd_per_table, self.key_bits,
             self._init_limit(), self.filter_freq, self.error_flag)
 
-    def dedup_lookup_capture(self, values_cat: torch.Tensor) -> DedupResult:
+    def dedup_lookup_capture(self, values_cat: torch.Tensor, pad=False,
+                             bump_step=True) -> DedupResult:
         """Sync-free, fixed-shape dedup+probe for hipGraph capture: all
         outputs are nnz-padded; the true unique count lives in a device
-        counter (m_dev) consumed by the padded pass B (tail slots = -1)."""
-        self.ext.bump_epoch(self._epoch_dev, self._step_dev)
+        counter (m_dev) consumed by the padded pass B (tail slots = -1).
+        With pad, PAD_KEY elements are not keys: inverse -1, no table
+        entry, no count. bump_step=False is for the second and later
+        lookups of one step (the dedup epoch must advance per lookup, the
+        device step once per step)."""
+        if bump_step:
+            self.ext.bump_epoch(self._epoch_dev, self._step_dev)
+        else:
+            self.ext.bump_epoch_only(self._epoch_dev)
         uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
-            values_cat, self._epoch_dev)
+            values_cat, self._epoch_dev, pad)
         # pass C first: its exact per-batch counts feed pass B's single
         # per-unique freq update (pass A is claim-only — hot keys no
         # longer serialize per-occurrence atomics)
-        inverse, counts, rank = self._dedup_count(occ_entry,
-                                                  values_cat.numel())
+        inverse, counts, rank = self._dedup_count(
+            occ_entry, values_cat.numel(),
+            pad_keys=values_cat if pad else None)
         slots = self._dedup_admit(centry_buf, uniq_buf, counts,
                                   m_dev=m_counter)
         return DedupResult(uniq_buf, inverse, counts, slots, rank, m_counter)
@@ -353,17 +363,18 @@ class HbmStorage:
         self._uniq_ratio = (r if self._uniq_ratio is None
                             else 0.7 * self._uniq_ratio + 0.3 * r)
 
-    def dedup_lookup(self, values_cat: torch.Tensor,
-                     step: int) -> DedupResult:
+    def dedup_lookup(self, values_cat: torch.Tensor, step: int,
+                     pad=False) -> DedupResult:
         """Fused unique+probe for a training step: raw (duplicated) keys in,
         exact-size uniq / inverse i32 / counts i32 / slots i32 out. One
         host sync (the unique count) — the same sync torch.unique pays —
-        and no sorts."""
+        and no sorts. With pad, PAD_KEY elements are not keys: they get
+        inverse -1 and leave the table, the counts and uniq untouched."""
         nnz = values_cat.numel()
         self._ensure_capacity(nnz)
         self._epoch += 1
         uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
-            values_cat)
+            values_cat, pad=pad)
         # one D2H sync (as torch.unique pays); piggyback the real counters
         # so capacity hints don't inflate by nnz per step (which caused
         # needless rehashes on high-uniqueness workloads)
@@ -372,10 +383,12 @@ class HbmStorage:
         m = int(c[0])
         self._entries_hint = int(c[1])
         self._slots_hint = int(c[2]) + m  # pass B may admit up to m slots
-        self.observe_uniq_ratio(m, nnz)
+        if not pad:  # pads would read as duplication the stream lacks
+            self.observe_uniq_ratio(m, nnz)
         uniq = uniq_buf[:m]
         # pass C first: exact counts feed pass B's per-unique freq update
-        inverse, counts, rank = self._dedup_count(occ_entry, m)
+        inverse, counts, rank = self._dedup_count(
+            occ_entry, m, pad_keys=values_cat if pad else None)
         slots = self._dedup_admit(centry_buf[:m], uniq, counts, step=step)
         return DedupResult(uniq, inverse, counts, slots, rank, None)
 
@@ -391,6 +404,14 @@ class HbmStorage:
     def gather(self, keys, slots, out_dtype=None):
         return self.ext.ev_gather(
             self.values, self.default_values, keys, slots,
+            self._no_permission_value(), self._use_no_permission(),
+            out_dtype or torch.float32)
+
+    def seq_gather_pad(self, keys, slots, inverse, out_dtype=None):
+        """[nnz, dim] rows of slots[inverse]; zero rows where inverse < 0.
+        keys/slots may be nnz-padded (capture)."""
+        return self.ext.seq_gather_pad(
+            self.values, self.default_values, keys, slots, inverse,
             self._no_permission_value(), self._use_no_permission(),
             out_dtype or torch.float32)
 

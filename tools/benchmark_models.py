@@ -3,6 +3,11 @@ harness analog). Runs each model for a fixed step count on the current
 device and writes a markdown table.
 
 Usage: python tools/benchmark_models.py [--steps 30] [--out profiles/...]
+       [--static-seq] [--no-graph]
+--static-seq builds din/dien/bst with static_seq=True (one padded lookup
+for sequence and target); din and bst then train as a captured hipGraph
+like the dense-feature models. dien stays eager: its auxiliary loss draws a
+permutation and branches on the host.
 Batch sizes follow the reference GPU benchmark config
 (modelzoo/benchmark/gpu/config.yaml: dlrm 8192, wide_and_deep 32768,
 deepfm 8192, dien 16384).
@@ -30,7 +35,12 @@ BATCH_SIZES = {
 DEFAULT_BATCH = 8192
 
 
-def bench_model(name, steps, warmup, device, use_graph=True):
+# sequence models that capture once their lookups are static-shape
+CAPTURABLE_SEQ = {"din", "bst"}
+
+
+def bench_model(name, steps, warmup, device, use_graph=True,
+                static_seq=False):
     from deeprec_amd.data.synthetic import CriteoSyntheticDataset
     from deeprec_amd.embedding.options import EmbeddingVariableOption
     from deeprec_amd.models import MODEL_REGISTRY, SEQUENCE_MODELS
@@ -38,9 +48,12 @@ def bench_model(name, steps, warmup, device, use_graph=True):
 
     torch.manual_seed(0)
     is_seq = name in SEQUENCE_MODELS
-    use_graph = use_graph and not is_seq and device.type == "cuda"
+    capturable = not is_seq or (static_seq and name in CAPTURABLE_SEQ)
+    use_graph = use_graph and capturable and device.type == "cuda"
     batch = BATCH_SIZES.get(name, DEFAULT_BATCH)
     kw = {}
+    if is_seq and static_seq:
+        kw["static_seq"] = True
     if use_graph:
         kw["ev_option"] = EmbeddingVariableOption(init_capacity=1 << 23)
     m = MODEL_REGISTRY[name](device=device, bf16=device.type == "cuda",
@@ -58,10 +71,18 @@ def bench_model(name, steps, warmup, device, use_graph=True):
     if use_graph:
         from deeprec_amd.training.graph_step import GraphedTrainStep
 
-        def loss_fn(model, dense, ids, labels):
-            return model.loss_fn(model(dense, ids), labels)
+        if is_seq:
+            def loss_fn(model, dense, ids, seq, target, labels):
+                logits = model(dense, ids[:, :model.num_sparse], seq,
+                               target)
+                return model.loss_fn(logits, labels)
+        else:
+            def loss_fn(model, dense, ids, labels):
+                return model.loss_fn(model(dense, ids), labels)
 
         gstep = GraphedTrainStep(m, opt, loss_fn, batches[0])
+        if is_seq and gstep.graph is None:
+            raise RuntimeError(f"{name}: graph capture failed")
 
         def step(i):
             gstep(batches[i % len(batches)])
@@ -110,6 +131,11 @@ def main():
     p.add_argument("--warmup", type=int, default=8)
     p.add_argument("--models", default=None)
     p.add_argument("--out", default=None)
+    p.add_argument("--static-seq", action="store_true",
+                   help="sequence models use the static-shape padded "
+                        "lookup; din and bst are captured")
+    p.add_argument("--no-graph", action="store_true",
+                   help="step eagerly even where capture is possible")
     args = p.parse_args()
     device = torch.device("cuda" if torch.cuda.is_available() else "cpu")
 
@@ -120,7 +146,9 @@ def main():
     for name in names:
         try:
             batch, sps, ms = bench_model(name, args.steps, args.warmup,
-                                         device)
+                                         device,
+                                         use_graph=not args.no_graph,
+                                         static_seq=args.static_seq)
             rows.append((name, batch, sps, ms))
             print(f"{name:18s} batch={batch:6d}  {sps:12.0f} samples/s  "
                   f"{ms:8.3f} ms/step", flush=True)
