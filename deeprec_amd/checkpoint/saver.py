@@ -219,15 +219,26 @@ class Saver:
             data = load_file(fn)
             keys = data["keys"]
             mask = self._owned_mask(ev, keys)
-            slab_rows = {k[len("slab/"):]: v[mask] for k, v in data.items()
-                         if k.startswith("slab/")}
-            self._precreate_slabs(base, data, slab_rows)
-            base.storage.import_(
-                keys[mask].to(base.device),
-                data["values"][mask].to(base.device),
-                data["freqs"][mask], data["versions"][mask],
-                slab_rows=slab_rows or None)
+            self._import_rows(base, data, mask)
             self._restore_filtered(base, ev, data)
+
+    def _import_rows(self, base, data, mask):
+        keys = data["keys"]
+        if getattr(base.storage, "inference_only", False):
+            # a serving-only storage has no optimizer state: no slabs are
+            # allocated, and the rows stay on the host so import_ can
+            # stage them to the device chunk by chunk
+            base.storage.import_(keys[mask], data["values"][mask],
+                                 data["freqs"][mask], data["versions"][mask])
+            return
+        slab_rows = {k[len("slab/"):]: v[mask] for k, v in data.items()
+                     if k.startswith("slab/")}
+        self._precreate_slabs(base, data, slab_rows)
+        base.storage.import_(
+            keys[mask].to(base.device),
+            data["values"][mask].to(base.device),
+            data["freqs"][mask], data["versions"][mask],
+            slab_rows=slab_rows or None)
 
     def _precreate_slabs(self, base, data, slab_rows):
         for n, rows in slab_rows.items():
@@ -260,15 +271,7 @@ class Saver:
                 data = load_file(fn)
                 keys = data["keys"]
                 mask = self._owned_mask(ev, keys)
-                slab_rows = {k[len("slab/"):]: v[mask]
-                             for k, v in data.items()
-                             if k.startswith("slab/")}
-                self._precreate_slabs(base, data, slab_rows)
-                base.storage.import_(
-                    keys[mask].to(base.device),
-                    data["values"][mask].to(base.device),
-                    data["freqs"][mask], data["versions"][mask],
-                    slab_rows=slab_rows or None)
+                self._import_rows(base, data, mask)
 
     # ------------- incremental -------------
     def incremental_save(self, directory: str, global_step: int) -> str:

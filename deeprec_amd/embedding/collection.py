@@ -111,7 +111,17 @@ class EmbeddingCollection:
         opt = copy.deepcopy(self.ev_option)
         dvd = max(1, opt.init_option.default_value_dim)
         opt.init_option.default_value_dim = dvd * self.n_tables
-        if self.device.type == "cuda":
+        from deeprec_amd.embedding.options import StorageType
+        fp8 = opt.storage_option.storage_type == StorageType.HBM_FP8
+        if fp8:
+            from deeprec_amd.ops.quant_backend import (QuantizedHbmStorage,
+                                                       require_cuda_for_fp8)
+            require_cuda_for_fp8(self.device, f"EmbeddingCollection {name!r}")
+            self.trainable = trainable = False
+            self.storage = QuantizedHbmStorage(embedding_dim, opt,
+                                               value_dtype, self.device,
+                                               generator)
+        elif self.device.type == "cuda":
             from deeprec_amd.ops.hip_backend import HbmStorage
             self.storage = HbmStorage(embedding_dim, opt, value_dtype,
                                       self.device, generator)
@@ -267,14 +277,9 @@ class EmbeddingCollection:
                     else torch.Tensor(),
                     self._combiner_ids, batch, self.n_tables,
                     out_dtype or torch.float32)
-            return self.storage.ext.group_pooled_fwd(
-                self.storage.values, self.storage.default_values, uniq, slots,
-                inverse, offsets_cat,
-                weights_cat if weights_cat is not None else torch.Tensor(),
-                self._combiner_ids, batch, self.n_tables, KEY_BITS,
-                self.storage._no_permission_value(),
-                self.storage._use_no_permission(),
-                out_dtype or torch.float32)
+            return self.storage.group_pooled_lookup(
+                uniq, slots, inverse, offsets_cat, weights_cat,
+                self._combiner_ids, batch, self.n_tables, out_dtype)
         # CPU reference: gather then pool per-table slices
         emb = (emb_override if emb_override is not None
                else self.storage.gather(uniq, slots))  # [m, D]

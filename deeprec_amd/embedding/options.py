@@ -30,6 +30,10 @@ class StorageType(enum.Enum):
     # compaction (reference: HbmDramSsdStorage, hbm_dram_ssd_storage.h);
     # storage_size = [hbm_bytes, dram_bytes], storage_path = SSD dir
     HBM_DRAM_SSD = 4
+    # inference-only HBM rows held as OCP e4m3 bytes + one fp32 scale per
+    # row, dequantized inside the gather/pool kernels
+    # (ops/quant_backend.py); the variable comes up with trainable=False
+    HBM_FP8 = 5
 
 
 class CacheStrategy(enum.Enum):

@@ -63,11 +63,20 @@ class EmbeddingVariable:
         self.device = torch.device(device or "cpu")
         self.trainable = trainable
 
+        from deeprec_amd.embedding.options import StorageType
+        st = self.ev_option.storage_option.storage_type
+        if st == StorageType.HBM_FP8:
+            from deeprec_amd.ops.quant_backend import require_cuda_for_fp8
+            require_cuda_for_fp8(self.device, f"EmbeddingVariable {name!r}")
+            self.trainable = trainable = False
         if self.device.type == "cuda":
             from deeprec_amd.ops.hip_backend import HbmStorage
-            from deeprec_amd.embedding.options import StorageType
-            st = self.ev_option.storage_option.storage_type
-            if st == StorageType.HBM_DRAM:
+            if st == StorageType.HBM_FP8:
+                from deeprec_amd.ops.quant_backend import QuantizedHbmStorage
+                self.storage = QuantizedHbmStorage(
+                    embedding_dim, self.ev_option, value_dtype, self.device,
+                    generator)
+            elif st == StorageType.HBM_DRAM:
                 from deeprec_amd.ops.hbm_dram_backend import HbmDramStorage
                 self.storage = HbmDramStorage(embedding_dim, self.ev_option,
                                               value_dtype, self.device,

@@ -21,6 +21,7 @@ Usage:
     from deeprec_amd.ops.fp8 import convert_mlp_to_fp8
     n = convert_mlp_to_fp8(model)         # swaps nn.Linear -> Fp8Linear
     ev_q, ev_scale = quantize_fp8_rows(ev.gather(keys))  # fp8 gather out
+    n = quantize_embeddings_fp8(model)    # HBM rows -> e4m3 + row scales
 """
 from __future__ import annotations
 
@@ -189,3 +190,57 @@ def convert_mlp_to_fp8(module: nn.Module) -> int:
         else:
             n += convert_mlp_to_fp8(child)
     return n
+
+
+def quantize_embeddings_fp8(obj) -> int:
+    """Convert trained HBM embeddings to fp8-resident serving storages, in
+    place and post-training (the sparse half of fp8 serving;
+    ops/quant_backend.py). ``obj`` is an EmbeddingVariable, an
+    EmbeddingCollection, or a module exposing ``embedding_variables()``.
+
+    Each ``.storage`` becomes a QuantizedHbmStorage that takes over the
+    hash table as it is; the fp32 slab is quantized per row (amax/448) in
+    chunks and dropped together with every optimizer slab, and the
+    variable becomes ``trainable=False`` (lookups with train=True serve).
+    Returns the number of storages converted; already-converted ones are
+    left alone. Raises NotImplementedError, naming the type, for anything
+    but a plain HBM EmbeddingVariable / EmbeddingCollection (multi-tier
+    and CPU storages, sharded wrappers, the extras.py variable kinds).
+    """
+    from deeprec_amd.embedding.collection import EmbeddingCollection
+    from deeprec_amd.embedding.variable import EmbeddingVariable
+    from deeprec_amd.ops.hip_backend import HbmStorage
+    from deeprec_amd.ops.quant_backend import QuantizedHbmStorage
+
+    from deeprec_amd.embedding.extras import MultiHashVariable
+
+    # a MultiHashVariable lists its Q/R variables like a model does, but
+    # it is one of the unsupported kinds, not a container to walk
+    targets = (list(obj.embedding_variables())
+               if hasattr(obj, "embedding_variables")
+               and not isinstance(obj, MultiHashVariable) else [obj])
+    todo = []
+    for t in targets:  # validate everything before touching anything
+        if type(t) not in (EmbeddingVariable, EmbeddingCollection):
+            raise NotImplementedError(
+                f"quantize_embeddings_fp8: {type(t).__name__} is not "
+                "supported (plain EmbeddingVariable / EmbeddingCollection "
+                "only)")
+        st = t.storage
+        if type(st) is QuantizedHbmStorage:
+            continue
+        if type(st) is not HbmStorage:
+            raise NotImplementedError(
+                f"quantize_embeddings_fp8: {t.name!r} is stored in a "
+                f"{type(st).__name__}; only the single-tier HBM storage "
+                "(HbmStorage) converts to fp8-resident rows")
+        if getattr(t, "graph_mode", False):
+            raise NotImplementedError(
+                f"quantize_embeddings_fp8: {t.name!r} is in graph mode "
+                "(captured training step); convert a non-captured model")
+        todo.append(t)
+    for t in todo:
+        t.storage = QuantizedHbmStorage.from_storage(t.storage)
+        t.trainable = False
+        t._anchor = torch.zeros((), device=t.device)
+    return len(todo)

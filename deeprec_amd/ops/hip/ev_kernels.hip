@@ -1280,12 +1280,6 @@ __global__ void k_apply_ftrl(float* __restrict__ w, float* __restrict__ n,
 
 #define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be on GPU")
 
-static inline int n_blocks(int64_t total, int block = kBlock) {
-  int64_t b = (total + block - 1) / block;
-  // keep the chip filled but bounded; grid-stride covers the tail
-  return (int)std::min<int64_t>(b, 65535);
-}
-
 // Zero n 4-byte words (fp32 or int32) on the stream; see k_zero_f32 for
 // why this is not hipMemsetAsync.
 static inline void zero_fill(void* p, int64_t n, hipStream_t stream) {
@@ -2103,12 +2097,14 @@ void register_dense(pybind11::module_& mod);      // dense_kernels.hip
 void register_gru(pybind11::module_& mod);        // gru_kernels.hip
 void register_attention(pybind11::module_& mod);  // attention_kernels.hip
 void register_fp8(pybind11::module_& mod);        // fp8_kernels.hip
+void register_quant_ev(pybind11::module_& mod);   // quant_ev_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_dense(mod);
   register_gru(mod);
   register_attention(mod);
   register_fp8(mod);
+  register_quant_ev(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);

@@ -8,11 +8,21 @@
 #include <hip/hip_runtime.h>
 #include <hip/hip_bf16.h>
 
+#include <algorithm>
 #include <cstdint>
 
 // current-stream accessor (ROCm ATen name)
 static inline hipStream_t current_hip_stream() {
   return at::hip::getCurrentHIPStreamMasqueradingAsCUDA().stream();
+}
+
+// Grid size for a grid-stride elementwise kernel: enough blocks to keep the
+// chip filled, capped at 65535.
+// NOTE every kernel launched through this cap MUST grid-stride: a plain
+// `if (i >= n) return` silently drops the tail past 65535 * block threads.
+static inline int n_blocks(int64_t total, int block = 256) {
+  int64_t b = (total + block - 1) / block;
+  return (int)std::min<int64_t>(b, 65535);
 }
 
 static __device__ __forceinline__ float bf2f_u16(short u) {

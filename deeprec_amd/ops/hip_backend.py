@@ -19,7 +19,7 @@ from deeprec_amd.embedding.options import (
     L2WeightEvict,
 )
 from deeprec_amd.ops.build_ext import require_extension
-from deeprec_amd.ops.common import COMBINER_ID, DedupResult
+from deeprec_amd.ops.common import COMBINER_ID, KEY_BITS, DedupResult
 
 _LOAD_FACTOR = 0.6
 
@@ -424,6 +424,19 @@ class HbmStorage:
             COMBINER_ID[combiner], self._no_permission_value(),
             self._use_no_permission(), out_dtype or torch.float32)
 
+    def group_pooled_lookup(self, keys, slots, inverse, offsets, weights,
+                            combiner_ids, batch, n_tables, out_dtype):
+        """The EmbeddingCollection forward: N tables' bags pooled in one
+        launch into the interleaved [batch, n_tables * dim] layout."""
+        return self.ext.group_pooled_fwd(
+            self.values, self.default_values, keys, slots,
+            inverse, offsets,
+            weights if weights is not None else torch.Tensor(),
+            combiner_ids, batch, n_tables, KEY_BITS,
+            self._no_permission_value(),
+            self._use_no_permission(),
+            out_dtype or torch.float32)
+
     def pooled_grad(self, grad_out, inverse, offsets, row_ids, m, combiner,
                     weights):
         return self.ext.pooled_bwd(
@@ -446,7 +459,7 @@ class HbmStorage:
             keep = torch.ones(keys.numel(), dtype=torch.bool,
                               device=self.device)
             has = slots >= 0
-            norms = self.values[slots[has].long()].norm(dim=1)
+            norms = self._row_norms(slots[has].long())
             kk = keep[has].clone()
             kk &= norms >= eo.l2_weight_threshold
             keep[has] = kk
@@ -457,6 +470,9 @@ class HbmStorage:
             return 0
         self._rebuild(keys[keep], slots[keep], freqs[keep], versions[keep])
         return n_evicted
+
+    def _row_norms(self, slots):
+        return self.values[slots].norm(dim=1)
 
     def _rebuild(self, keys, slots, freqs, versions):
         """Compact: renumber admitted slots densely, rewrite slabs/table."""
@@ -501,7 +517,19 @@ class HbmStorage:
             return
         keys = keys.to(self.device)
         values = values.to(self.device, torch.float32)
-        # existing keys keep their slots; new keys get fresh ones
+        slots = self._import_entries(keys, freqs, versions)
+        self.values[slots.long()] = values
+        if slab_rows is not None:
+            for name, rows in slab_rows.items():
+                self.get_slab(name, rows.shape[1], 0.0)[slots.long()] = \
+                    rows.to(self.device)
+        self._check_error()
+        self._sync_counters()
+
+    def _import_entries(self, keys, freqs, versions):
+        """Table half of an import: existing keys keep their slots, new
+        keys get fresh ones; returns the slot of every key."""
+        m = keys.numel()
         existing = self.lookup(keys)
         is_new = existing < 0
         n_new = int(is_new.sum())
@@ -521,13 +549,7 @@ class HbmStorage:
             else torch.Tensor(),
             self.ht_keys, self.ht_slot, self.ht_freq, self.ht_version,
             self.entry_counter, self.error_flag)
-        self.values[slots.long()] = values
-        if slab_rows is not None:
-            for name, rows in slab_rows.items():
-                self.get_slab(name, rows.shape[1], 0.0)[slots.long()] = \
-                    rows.to(self.device)
-        self._check_error()
-        self._sync_counters()
+        return slots
 
     def import_filtered(self, keys, freqs):
         """Restore sub-threshold admission counters (reference capability:
@@ -591,6 +613,10 @@ class HbmStorage:
 # ---------------- optimizer dispatch ----------------
 
 def sparse_apply(name: str, storage: HbmStorage, slots, grad, hyper: dict):
+    if getattr(storage, "inference_only", False):
+        raise RuntimeError(
+            f"{type(storage).__name__} is inference-only: its rows are "
+            "quantized and cannot take a sparse optimizer apply")
     ext = storage.ext
     grad = grad.float().contiguous()
     slots = slots.to(torch.int32)

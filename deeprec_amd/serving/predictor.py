@@ -58,9 +58,21 @@ class Predictor:
 
     def __init__(self, model, checkpoint_dir: str,
                  num_sessions: int = 2, device=None,
-                 remote_sparse: bool = False, fp8_mlp: bool = False):
+                 remote_sparse: bool = False, fp8_mlp: bool = False,
+                 fp8_embeddings: bool = False):
         self.model = model
         self.dir = checkpoint_dir
+        # fp8_embeddings: hold the embedding rows as e4m3 bytes + per-row
+        # scales (ops/quant_backend.py). The still-empty storages are
+        # converted before the first restore, so full checkpoints and
+        # deltas alike land through import_ and are quantized on the way
+        # in — nothing to revert around an update
+        if fp8_embeddings:
+            if remote_sparse:
+                raise ValueError("fp8_embeddings converts the model's local "
+                                 "embedding storages; remote_sparse has none")
+            from deeprec_amd.ops.fp8 import quantize_embeddings_fp8
+            quantize_embeddings_fp8(model)
         # fp8_mlp: serve the dense MLPs as OCP e4m3 (ops/fp8.py) — the
         # converter is reverted around full model updates so restores
         # land in the fp32 originals, then re-quantized

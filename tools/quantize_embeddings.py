@@ -90,3 +90,18 @@ def load_quantized(fn: str):
         raise ValueError(f"{fn}: no quantized values tensor")
     return (data["keys"], values, data.get("freqs"),
             data.get("versions"))
+
+
+def load_quantized_raw(fn: str):
+    """Load a `.fp8.safetensors` EV file WITHOUT dequantizing: (keys,
+    e4m3 bytes uint8 [n, dim], fp32 scales [n], freqs, versions) — the
+    arguments of `QuantizedHbmStorage.import_quantized`, which serves the
+    bytes as they are (StorageType.HBM_FP8). int8 files have no resident
+    form; load those with `load_quantized`."""
+    from safetensors.torch import load_file
+    data = load_file(fn)
+    if "values_fp8" not in data:
+        raise ValueError(f"{fn}: no values_fp8 tensor (only the fp8 format "
+                         "is served resident; int8 is file-only)")
+    return (data["keys"], data["values_fp8"], data["values_scale"],
+            data.get("freqs"), data.get("versions"))
