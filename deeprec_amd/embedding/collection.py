@@ -56,11 +56,14 @@ def prep_backward(storage, inverse, counts, rank=None):
     `rank` is the DedupResult.rank that came with this `inverse`."""
     m = counts.numel()
     c32 = counts.to(torch.int32)
-    bounds = torch.zeros(m + 1, dtype=torch.int32, device=inverse.device)
-    bounds[1:] = c32.cumsum(0)
     if inverse.device.type != "cuda":
+        bounds = torch.zeros(m + 1, dtype=torch.int32, device=inverse.device)
+        bounds[1:] = c32.cumsum(0)
         order = torch.argsort(inverse.long()).to(torch.int32)
-    elif rank is not None:
+        return order, bounds
+    # int32 scan in two launches of ours (was: fill, rocprim scan, cast)
+    bounds = storage.ext.csr_bounds(c32.contiguous())
+    if rank is not None:
         # pass C already recorded each occurrence's rank within its key,
         # so order is a direct scatter (no atomic-cursor pass over nnz)
         order = storage.ext.csr_scatter(inverse, rank, bounds,
@@ -229,6 +232,12 @@ class EmbeddingCollection:
         """(values_cat, offsets, row_ids, row_coeff) for ids [batch,
         n_tables], one id per table per sample. Everything but the
         tagged keys is cached per batch size."""
+        offsets, row_ids, row_coeff, tags = self._matrix_static(ids)
+        return ids.t().reshape(-1) + tags, offsets, row_ids, row_coeff
+
+    def _matrix_static(self, ids: torch.Tensor):
+        """(offsets, row_ids, row_coeff, tags): the part of matrix_inputs
+        that depends on the batch size alone."""
         batch, n = ids.shape
         assert n == self.n_tables
         cache = self._matrix_cache.get(batch)
@@ -242,8 +251,7 @@ class EmbeddingCollection:
                 (torch.arange(n, dtype=torch.int64, device=dev)
                  << KEY_BITS).repeat_interleave(batch))
             self._matrix_cache[batch] = cache
-        offsets, row_ids, row_coeff, tags = cache
-        return ids.t().reshape(-1) + tags, offsets, row_ids, row_coeff
+        return cache
 
     def lookup_matrix(self, ids: torch.Tensor, out_dtype=None,
                       train: bool = True) -> torch.Tensor:
@@ -251,11 +259,19 @@ class EmbeddingCollection:
         per sample, the Criteo layout). All ragged glue (offsets, row ids,
         combiner coeffs, table tags) is cached per batch size, so a step
         costs: 1 transpose+add, 1 unique, the probe, the fused fwd/bwd and
-        the apply."""
+        the apply. A captured training step on a storage that offers
+        dedup_lookup_capture_matrix skips the transpose+add as well: pass A
+        forms the composite keys from `ids` itself."""
         batch = ids.shape[0]
-        values_cat, offsets, row_ids, row_coeff = self.matrix_inputs(ids)
         train = train and self.trainable
-        d = self._dedup_and_probe(values_cat, train)
+        if (train and self.graph_mode and not self._record_sparse_ids
+                and ids.dtype == torch.int64 and ids.is_contiguous()
+                and hasattr(self.storage, "dedup_lookup_capture_matrix")):
+            offsets, row_ids, row_coeff, _ = self._matrix_static(ids)
+            d = self.storage.dedup_lookup_capture_matrix(ids)
+        else:
+            values_cat, offsets, row_ids, row_coeff = self.matrix_inputs(ids)
+            d = self._dedup_and_probe(values_cat, train)
         if not train:
             return self._forward(d.uniq, d.slots, d.inverse, offsets, None,
                                  batch, out_dtype)
@@ -413,4 +429,5 @@ class _CollectionLookup(torch.autograd.Function):
                                      row_coeff, uniq.numel(), ctx.batch,
                                      ctx.identity_rows)
         coll.accumulate_grad(slots, uniq, grad_unique)
-        return (torch.zeros_like(coll._anchor),) + (None,) * 13
+        # the anchor only ties this node into the graph; it has no gradient
+        return (None,) * 14

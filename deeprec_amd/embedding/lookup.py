@@ -68,7 +68,7 @@ class _PooledLookup(torch.autograd.Function):
                 grad_out, inverse, offsets, row_ids, uniq.numel(),
                 ctx.combiner, ctx.weights)
         ev.accumulate_grad(slots, uniq, grad_unique)
-        return (torch.zeros_like(ctx.ev._anchor),) + (None,) * 10
+        return (None,) * 11
 
 
 def _chunked_ev_backward(ev, grad_out, inverse, offsets, row_ids, counts,
@@ -176,7 +176,7 @@ class _PaddedSeqLookup(torch.autograd.Function):
             grad_out.contiguous(), order, inverse, none, none, none,
             uniq.numel(), inverse.numel(), 1, ev.dim, True, 0)
         ev.accumulate_grad(slots, uniq, grad_unique)
-        return (torch.zeros_like(ev._anchor),) + (None,) * 6
+        return (None,) * 7
 
 
 def masked_padded_lookup(ev, ids: torch.Tensor, pad_id: int, out_dtype=None,

@@ -97,5 +97,5 @@ class RecModelBase(nn.Module):
         return contextlib.nullcontext()
 
     def loss_fn(self, logits: torch.Tensor, labels: torch.Tensor):
-        return nn.functional.binary_cross_entropy_with_logits(
-            logits.float(), labels.float())
+        from deeprec_amd.ops.fused_loss import bce_with_logits_mean
+        return bce_with_logits_mean(logits.float(), labels.float())

@@ -143,4 +143,5 @@ class DLRM(nn.Module):
         return logits.squeeze(1).float()
 
     def loss_fn(self, logits: torch.Tensor, labels: torch.Tensor):
-        return nn.functional.binary_cross_entropy_with_logits(logits, labels)
+        from deeprec_amd.ops.fused_loss import bce_with_logits_mean
+        return bce_with_logits_mean(logits, labels)

@@ -23,7 +23,8 @@ _SOURCES = [os.path.join(_HERE, "hip", "ev_kernels.hip"),
             os.path.join(_HERE, "hip", "gru_kernels.hip"),
             os.path.join(_HERE, "hip", "attention_kernels.hip"),
             os.path.join(_HERE, "hip", "fp8_kernels.hip"),
-            os.path.join(_HERE, "hip", "quant_ev_kernels.hip")]
+            os.path.join(_HERE, "hip", "quant_ev_kernels.hip"),
+            os.path.join(_HERE, "hip", "loss_kernels.hip")]
 _HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 _ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 

@@ -220,19 +220,34 @@ __global__ void k_insert_bulk(
 // at all — no probe, no claim, no table entry; it records entry -1 for
 // pass C (which skips it by key) and moves on. One body for both
 // instantiations, so the claim logic cannot drift.
-template <bool SKIP_PAD>
+//
+// MATRIX (the one-id-per-table layout): `keys` is the id matrix
+// ids[batch, n_tables] itself, row-major, and occurrence j = t * batch + b
+// has the composite key ids[b * n_tables + t] + (t << key_bits) — the
+// table-major key array the collection would otherwise build with a
+// transposing copy and an add. Reads are strided, the occ_entry write
+// stays coalesced; pass A is bound by its table probes either way.
+template <bool SKIP_PAD, bool MATRIX = false>
 __global__ void k_dedup_pass_a(
     const int64_t* __restrict__ keys, int nnz, int64_t* __restrict__ ht_keys,
     int32_t* __restrict__ ht_epoch, int32_t* __restrict__ ht_compact,
     int64_t cap_mask, const int32_t* __restrict__ epoch_dev, int epoch_val,
     int32_t* __restrict__ entry_counter, int32_t* __restrict__ m_counter,
     int64_t* __restrict__ uniq_keys, int64_t* __restrict__ compact_entry,
-    int64_t* __restrict__ occ_entry, int32_t* __restrict__ error_flag) {
+    int64_t* __restrict__ occ_entry, int32_t* __restrict__ error_flag,
+    int batch = 0, int n_tables = 0, int key_bits = 0) {
   const int epoch = epoch_dev ? *epoch_dev : epoch_val;
   int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   int64_t stride = gridDim.x * (int64_t)blockDim.x;
   for (; j < nnz; j += stride) {
-    const int64_t key = keys[j];
+    int64_t key;
+    if constexpr (MATRIX) {
+      const int t = (int)j / batch;
+      const int b = (int)j - t * batch;
+      key = keys[(int64_t)b * n_tables + t] + ((int64_t)t << key_bits);
+    } else {
+      key = keys[j];
+    }
     if constexpr (SKIP_PAD) {
       if (key == PAD_KEY) {
         occ_entry[j] = -1;
@@ -268,6 +283,28 @@ __global__ void k_bump_epoch(int32_t* __restrict__ epoch_dev,
     epoch_dev[0] += 1;
     step_dev[0] += 1;
   }
+}
+
+// Prologue of a captured dedup, one launch for what were three: bump the
+// epoch (and the step when step_dev is given, as k_bump_epoch does), zero
+// the unique counter pass A claims from, and zero the n per-key counters
+// pass C adds into. A kernel and not a memset for the reason k_zero_f32
+// gives. Nothing here reads what it writes, so no ordering is needed
+// inside the launch.
+__global__ void k_dedup_begin(int32_t* __restrict__ epoch_dev,
+                              int64_t* __restrict__ step_dev,
+                              int32_t* __restrict__ m_counter,
+                              int32_t* __restrict__ counts, int64_t n) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) {
+    epoch_dev[0] += 1;
+    if (step_dev) step_dev[0] += 1;
+    m_counter[0] = 0;
+    for (int64_t j = n & ~3LL; j < n; ++j) counts[j] = 0;
+  }
+  int64_t i = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) * 4;
+  int64_t stride = gridDim.x * (int64_t)blockDim.x * 4;
+  for (; i + 3 < n; i += stride)
+    *reinterpret_cast<int4*>(counts + i) = make_int4(0, 0, 0, 0);
 }
 
 // Pass B (per unique key): freq/version bookkeeping (one write per
@@ -589,6 +626,89 @@ __global__ void k_dedup_pass_c(
       // key, letting the CSR order build become a direct scatter
       // (k_csr_scatter) instead of a second atomic-cursor pass
       rank[j] = valid ? base + g.pos : 0;
+    }
+  }
+}
+
+// CSR bounds: bounds[0] = 0, bounds[i + 1] = counts[0] + ... + counts[i],
+// int32 throughout, in two launches. k_tile_sums writes one total per tile
+// of kScanTile counts; k_csr_bounds then has each block add up the tile
+// totals in front of its tile and scan the tile itself. No block ever
+// waits for another (no look-back, no flags): the only dependency is the
+// kernel boundary. Both grid-stride over tiles, so the grid cap
+// (kScanMaxBlocks) bounds nothing but parallelism.
+constexpr int kScanPer = 4;
+constexpr int kScanTile = kBlock * kScanPer;
+constexpr int kScanMaxBlocks = 1024;
+
+// Sum of v over the block, returned to every thread. `red` holds kBlock
+// ints; two barriers, so back-to-back calls may reuse it.
+DEV_INLINE int block_sum_i32(int v, int* __restrict__ red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = kBlock / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  const int total = red[0];
+  __syncthreads();
+  return total;
+}
+
+__global__ __launch_bounds__(kBlock) void k_tile_sums(
+    const int32_t* __restrict__ counts, int64_t m, int n_tiles,
+    int32_t* __restrict__ tile_sums) {
+  __shared__ int red[kBlock];
+  for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    const int64_t i0 = (int64_t)t * kScanTile + threadIdx.x * kScanPer;
+    int v = 0;
+#pragma unroll
+    for (int k = 0; k < kScanPer; ++k)
+      if (i0 + k < m) v += counts[i0 + k];
+    const int total = block_sum_i32(v, red);
+    if (threadIdx.x == 0) tile_sums[t] = total;
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void k_csr_bounds(
+    const int32_t* __restrict__ counts, int64_t m, int n_tiles,
+    const int32_t* __restrict__ tile_sums, int32_t* __restrict__ bounds) {
+  __shared__ int red[kBlock];
+  __shared__ int scan[2][kBlock];
+  if (blockIdx.x == 0 && threadIdx.x == 0) bounds[0] = 0;
+  int base = 0;   // sum of the tile totals in [0, summed)
+  int summed = 0;
+  for (int t = blockIdx.x; t < n_tiles; t += gridDim.x) {
+    int part = 0;
+    for (int u = summed + threadIdx.x; u < t; u += kBlock)
+      part += tile_sums[u];
+    base += block_sum_i32(part, red);
+    summed = t;
+    const int64_t i0 = (int64_t)t * kScanTile + threadIdx.x * kScanPer;
+    int c[kScanPer];
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < kScanPer; ++k) {
+      c[k] = i0 + k < m ? counts[i0 + k] : 0;
+      mine += c[k];
+    }
+    // inclusive Hillis-Steele scan of the per-thread totals
+    int cur = 0;
+    scan[0][threadIdx.x] = mine;
+    __syncthreads();
+    for (int d = 1; d < kBlock; d <<= 1) {
+      int v = scan[cur][threadIdx.x];
+      if ((int)threadIdx.x >= d) v += scan[cur][threadIdx.x - d];
+      scan[cur ^ 1][threadIdx.x] = v;
+      cur ^= 1;
+      __syncthreads();
+    }
+    int run = base + scan[cur][threadIdx.x] - mine;
+    __syncthreads();  // scan[] is rewritten by the next tile
+#pragma unroll
+    for (int k = 0; k < kScanPer; ++k) {
+      run += c[k];
+      if (i0 + k < m) bounds[i0 + k + 1] = run;
     }
   }
 }
@@ -1325,23 +1445,25 @@ static inline const T* opt_ptr(const c10::optional<torch::Tensor>& t) {
   return t.has_value() ? t->data_ptr<T>() : nullptr;
 }
 
-template <bool SKIP_PAD>
+template <bool SKIP_PAD, bool MATRIX = false>
 static torch::Tensor dedup_a_impl(
     torch::Tensor keys, torch::Tensor ht_keys, torch::Tensor ht_epoch,
     torch::Tensor ht_compact, c10::optional<torch::Tensor> epoch_dev,
     int64_t epoch, torch::Tensor entry_counter, torch::Tensor m_counter,
     torch::Tensor uniq_keys, torch::Tensor compact_entry,
-    torch::Tensor occ_entry, torch::Tensor error_flag) {
+    torch::Tensor occ_entry, torch::Tensor error_flag, int batch = 0,
+    int n_tables = 0, int key_bits = 0) {
   int64_t nnz = keys.numel();
   if (nnz == 0) return m_counter;
   auto stream = current_hip_stream();
-  k_dedup_pass_a<SKIP_PAD><<<n_blocks(nnz), kBlock, 0, stream>>>(
+  k_dedup_pass_a<SKIP_PAD, MATRIX><<<n_blocks(nnz), kBlock, 0, stream>>>(
       keys.data_ptr<int64_t>(), (int)nnz, ht_keys.data_ptr<int64_t>(),
       ht_epoch.data_ptr<int32_t>(), ht_compact.data_ptr<int32_t>(),
       ht_keys.numel() - 1, opt_ptr<int32_t>(epoch_dev), (int)epoch,
       entry_counter.data_ptr<int32_t>(), m_counter.data_ptr<int32_t>(),
       uniq_keys.data_ptr<int64_t>(), compact_entry.data_ptr<int64_t>(),
-      occ_entry.data_ptr<int64_t>(), error_flag.data_ptr<int32_t>());
+      occ_entry.data_ptr<int64_t>(), error_flag.data_ptr<int32_t>(), batch,
+      n_tables, key_bits);
   return m_counter;
 }
 
@@ -1370,6 +1492,34 @@ torch::Tensor ht_dedup_a_pad(torch::Tensor keys, torch::Tensor ht_keys,
   return dedup_a_impl<true>(keys, ht_keys, ht_epoch, ht_compact, epoch_dev,
                             epoch, entry_counter, m_counter, uniq_keys,
                             compact_entry, occ_entry, error_flag);
+}
+
+// Pass A straight from the id matrix ids[batch, n_tables] (int64,
+// contiguous): occurrence t * batch + b is ids[b, t] + (t << key_bits), the
+// order EmbeddingCollection.matrix_inputs builds, without building it.
+torch::Tensor ht_dedup_a_matrix(
+    torch::Tensor ids, int64_t key_bits, torch::Tensor ht_keys,
+    torch::Tensor ht_epoch, torch::Tensor ht_compact,
+    c10::optional<torch::Tensor> epoch_dev, int64_t epoch,
+    torch::Tensor entry_counter, torch::Tensor m_counter,
+    torch::Tensor uniq_keys, torch::Tensor compact_entry,
+    torch::Tensor occ_entry, torch::Tensor error_flag) {
+  CHECK_DEV(ids);
+  TORCH_CHECK(ids.dim() == 2 && ids.is_contiguous() &&
+                  ids.scalar_type() == torch::kInt64,
+              "ht_dedup_a_matrix: ids must be contiguous int64 [batch, n]");
+  TORCH_CHECK(ids.numel() <= INT32_MAX, "ht_dedup_a_matrix: too many ids");
+  TORCH_CHECK(key_bits > 0 && key_bits < 63 &&
+                  ids.size(1) <= ((int64_t)1 << (63 - key_bits)),
+              "ht_dedup_a_matrix: table tag does not fit above key_bits");
+  TORCH_CHECK(uniq_keys.numel() >= ids.numel() &&
+                  compact_entry.numel() >= ids.numel() &&
+                  occ_entry.numel() >= ids.numel(),
+              "ht_dedup_a_matrix: output buffers are smaller than ids");
+  return dedup_a_impl<false, true>(
+      ids, ht_keys, ht_epoch, ht_compact, epoch_dev, epoch, entry_counter,
+      m_counter, uniq_keys, compact_entry, occ_entry, error_flag,
+      (int)ids.size(0), (int)ids.size(1), (int)key_bits);
 }
 
 torch::Tensor ht_dedup_b(torch::Tensor compact_entry, torch::Tensor uniq_keys,
@@ -1408,6 +1558,26 @@ void bump_epoch(torch::Tensor epoch_dev, torch::Tensor step_dev) {
 void bump_epoch_only(torch::Tensor epoch_dev) {
   k_bump_epoch_only<<<1, 64, 0, current_hip_stream()>>>(
       epoch_dev.data_ptr<int32_t>());
+}
+
+// step_dev None: epoch only (a second lookup within one step).
+void dedup_begin(torch::Tensor epoch_dev,
+                 c10::optional<torch::Tensor> step_dev,
+                 torch::Tensor m_counter, torch::Tensor counts) {
+  CHECK_DEV(counts);
+  TORCH_CHECK(counts.scalar_type() == torch::kInt32 &&
+                  counts.is_contiguous() &&
+                  m_counter.scalar_type() == torch::kInt32 &&
+                  m_counter.numel() == 1,
+              "dedup_begin: counts int32 contiguous, m_counter int32 [1]");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(counts.data_ptr()) % 16 == 0,
+              "dedup_begin: counts must be 16-byte aligned");
+  const int64_t n = counts.numel();
+  k_dedup_begin<<<std::max(1, n_blocks((n + 3) / 4)), kBlock, 0,
+                  current_hip_stream()>>>(
+      epoch_dev.data_ptr<int32_t>(),
+      step_dev.has_value() ? step_dev->data_ptr<int64_t>() : nullptr,
+      m_counter.data_ptr<int32_t>(), counts.data_ptr<int32_t>(), n);
 }
 
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> route_pad(
@@ -1521,21 +1691,54 @@ torch::Tensor rows_to_padded(torch::Tensor src, torch::Tensor route_pos,
 }
 
 // keys: None, or the received keys whose PAD_KEY elements pass C skips.
+// counts_in: None, or the m counters the caller has already zeroed
+// (dedup_begin) — pass C then adds into them without a fill of its own.
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> ht_dedup_c(
     c10::optional<torch::Tensor> keys, torch::Tensor occ_entry,
-    torch::Tensor ht_compact, int64_t m) {
+    torch::Tensor ht_compact, int64_t m,
+    c10::optional<torch::Tensor> counts_in) {
   int64_t nnz = occ_entry.numel();
   auto inverse = torch::empty({nnz}, ht_compact.options());
   auto rank = torch::empty({nnz}, ht_compact.options());
-  auto counts = torch::empty({m}, ht_compact.options());
+  if (counts_in.has_value())
+    TORCH_CHECK(counts_in->numel() == m && counts_in->is_contiguous() &&
+                    counts_in->scalar_type() == torch::kInt32 &&
+                    counts_in->is_cuda(),
+                "ht_dedup_c: counts must be int32 [m] on GPU");
+  auto counts = counts_in.has_value()
+                    ? *counts_in
+                    : torch::empty({m}, ht_compact.options());
   if (nnz == 0) return {inverse, counts, rank};
   auto stream = current_hip_stream();
-  zero_fill(counts.data_ptr<int32_t>(), m, stream);
+  if (!counts_in.has_value()) zero_fill(counts.data_ptr<int32_t>(), m, stream);
   k_dedup_pass_c<<<n_blocks(nnz), kBlock, 0, stream>>>(
       opt_ptr<int64_t>(keys), occ_entry.data_ptr<int64_t>(), (int)nnz,
       ht_compact.data_ptr<int32_t>(), inverse.data_ptr<int32_t>(),
       counts.data_ptr<int32_t>(), rank.data_ptr<int32_t>());
   return {inverse, counts, rank};
+}
+
+// Exclusive prefix sum of int32 counts [m] -> int32 bounds [m + 1].
+torch::Tensor csr_bounds(torch::Tensor counts) {
+  CHECK_DEV(counts);
+  TORCH_CHECK(counts.scalar_type() == torch::kInt32 && counts.dim() == 1 &&
+                  counts.is_contiguous(),
+              "csr_bounds: counts must be contiguous int32 [m]");
+  const int64_t m = counts.numel();
+  if (m == 0) return torch::zeros({1}, counts.options());
+  auto bounds = torch::empty({m + 1}, counts.options());
+  const int64_t n_tiles = (m + kScanTile - 1) / kScanTile;
+  TORCH_CHECK(n_tiles <= INT32_MAX, "csr_bounds: too many counts");
+  auto tile_sums = torch::empty({n_tiles}, counts.options());
+  const int grid = (int)std::min<int64_t>(n_tiles, kScanMaxBlocks);
+  auto stream = current_hip_stream();
+  k_tile_sums<<<grid, kBlock, 0, stream>>>(
+      counts.data_ptr<int32_t>(), m, (int)n_tiles,
+      tile_sums.data_ptr<int32_t>());
+  k_csr_bounds<<<grid, kBlock, 0, stream>>>(
+      counts.data_ptr<int32_t>(), m, (int)n_tiles,
+      tile_sums.data_ptr<int32_t>(), bounds.data_ptr<int32_t>());
+  return bounds;
 }
 
 torch::Tensor csr_scatter(torch::Tensor inverse, torch::Tensor rank,
@@ -2098,6 +2301,7 @@ void register_gru(pybind11::module_& mod);        // gru_kernels.hip
 void register_attention(pybind11::module_& mod);  // attention_kernels.hip
 void register_fp8(pybind11::module_& mod);        // fp8_kernels.hip
 void register_quant_ev(pybind11::module_& mod);   // quant_ev_kernels.hip
+void register_loss(pybind11::module_& mod);       // loss_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_dense(mod);
@@ -2105,12 +2309,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_attention(mod);
   register_fp8(mod);
   register_quant_ev(mod);
+  register_loss(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);
+  mod.def("ht_dedup_a_matrix", &ht_dedup_a_matrix);
   mod.def("ht_dedup_b", &ht_dedup_b);
   mod.def("bump_epoch", &bump_epoch);
   mod.def("bump_epoch_only", &bump_epoch_only);
+  mod.def("dedup_begin", &dedup_begin);
   mod.def("route_pad", &route_pad);
   mod.def("rows_to_padded", &rows_to_padded);
   mod.def("slots_gather_pad", &slots_gather_pad);
@@ -2119,7 +2326,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("compose_i32", &compose_i32);
   mod.def("gather_host_rows", &gather_host_rows);
   mod.def("scatter_host_rows", &scatter_host_rows);
-  mod.def("ht_dedup_c", &ht_dedup_c);
+  mod.def("ht_dedup_c", &ht_dedup_c, pybind11::arg("keys"),
+          pybind11::arg("occ_entry"), pybind11::arg("ht_compact"),
+          pybind11::arg("m"), pybind11::arg("counts") = pybind11::none());
+  mod.def("csr_bounds", &csr_bounds);
+  mod.attr("CSR_SCAN_TILE") = kScanTile;
+  mod.attr("CSR_SCAN_MAX_BLOCKS") = kScanMaxBlocks;
   mod.def("csr_order", &csr_order);
   mod.def("csr_scatter", &csr_scatter);
   mod.def("csr_scatter_pad", &csr_scatter_pad);

@@ -247,29 +247,54 @@ class HbmStorage:
                                       dtype=torch.int64, device=self.device)
 
     # ---------------- fused hash dedup: the three passes ----------------
-    def _dedup_claim(self, keys: torch.Tensor, epoch_dev=None, pad=False):
+    def _dedup_begin(self, nnz: int, bump_step: bool = True):
+        """Prologue of a captured dedup, one launch: advance the device
+        epoch (and step), and hand back a zeroed unique counter and the
+        zeroed per-key counters pass C adds into. -> (m_counter, counts)."""
+        m_counter = torch.empty(1, dtype=torch.int32, device=self.device)
+        counts = torch.empty(nnz, dtype=torch.int32, device=self.device)
+        self.ext.dedup_begin(self._epoch_dev,
+                             self._step_dev if bump_step else None,
+                             m_counter, counts)
+        return m_counter, counts
+
+    def _dedup_claim(self, keys: torch.Tensor, epoch_dev=None, pad=False,
+                     m_counter=None, matrix=False):
         """Pass A: allocate the step's buffers, then find-or-insert every
         occurrence and claim a compact index per unique key. The epoch is
         the device scalar when given (capture), else the host counter.
         With pad, PAD_KEY occurrences touch nothing (occ_entry -1).
+        With matrix, `keys` is the id matrix [batch, n_tables] and pass A
+        forms the table-major composite keys itself. m_counter is the
+        zeroed counter from _dedup_begin, or None to allocate one here.
         Returns (uniq_buf, centry_buf, occ_entry, m_counter); the first
         three are nnz-padded, m_counter is the device unique count."""
         nnz = keys.numel()
         uniq_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
         centry_buf = torch.empty(nnz, dtype=torch.int64, device=self.device)
         occ_entry = torch.empty(nnz, dtype=torch.int64, device=self.device)
-        m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
-        pass_a = self.ext.ht_dedup_a_pad if pad else self.ext.ht_dedup_a
-        pass_a(keys, self.ht_keys, self.ht_epoch, self.ht_compact,
-               epoch_dev, self._epoch, self.entry_counter, m_counter,
-               uniq_buf, centry_buf, occ_entry, self.error_flag)
+        if m_counter is None:
+            m_counter = torch.zeros(1, dtype=torch.int32, device=self.device)
+        rest = (self.ht_keys, self.ht_epoch, self.ht_compact, epoch_dev,
+                self._epoch, self.entry_counter, m_counter, uniq_buf,
+                centry_buf, occ_entry, self.error_flag)
+        if matrix:
+            assert not pad, "the id matrix holds no pads"
+            self.ext.ht_dedup_a_matrix(keys, self.key_bits, *rest)
+        elif pad:
+            self.ext.ht_dedup_a_pad(keys, *rest)
+        else:
+            self.ext.ht_dedup_a(keys, *rest)
         return uniq_buf, centry_buf, occ_entry, m_counter
 
-    def _dedup_count(self, occ_entry: torch.Tensor, m: int, pad_keys=None):
+    def _dedup_count(self, occ_entry: torch.Tensor, m: int, pad_keys=None,
+                     counts=None):
         """Pass C: (inverse, counts [m], rank) from the entries pass A
         recorded (index-direct: no table re-probe). With pad_keys, PAD_KEY
-        elements get inverse -1 and touch no counter."""
-        return self.ext.ht_dedup_c(pad_keys, occ_entry, self.ht_compact, m)
+        elements get inverse -1 and touch no counter. `counts` is the
+        zeroed buffer from _dedup_begin, or None to allocate and zero one."""
+        return self.ext.ht_dedup_c(pad_keys, occ_entry, self.ht_compact, m,
+                                   counts)
 
     def _dedup_admit(self, centry, uniq, counts, step=0, m_dev=None):
         """Pass B: one freq/version update per unique key from pass C's
@@ -285,29 +310,38 @@ class HbmStorage:
             self._init_limit(), self.filter_freq, self.error_flag)
 
     def dedup_lookup_capture(self, values_cat: torch.Tensor, pad=False,
-                             bump_step=True) -> DedupResult:
+                             bump_step=True, matrix=False) -> DedupResult:
         """Sync-free, fixed-shape dedup+probe for hipGraph capture: all
         outputs are nnz-padded; the true unique count lives in a device
         counter (m_dev) consumed by the padded pass B (tail slots = -1).
         With pad, PAD_KEY elements are not keys: inverse -1, no table
         entry, no count. bump_step=False is for the second and later
         lookups of one step (the dedup epoch must advance per lookup, the
-        device step once per step)."""
-        if bump_step:
-            self.ext.bump_epoch(self._epoch_dev, self._step_dev)
-        else:
-            self.ext.bump_epoch_only(self._epoch_dev)
+        device step once per step). With matrix, values_cat is the id
+        matrix [batch, n_tables] and the composite keys are formed inside
+        pass A (occurrence order t * batch + b, as matrix_inputs builds)."""
+        nnz = values_cat.numel()
+        m_counter, counts = self._dedup_begin(nnz, bump_step)
         uniq_buf, centry_buf, occ_entry, m_counter = self._dedup_claim(
-            values_cat, self._epoch_dev, pad)
+            values_cat, self._epoch_dev, pad, m_counter, matrix)
         # pass C first: its exact per-batch counts feed pass B's single
         # per-unique freq update (pass A is claim-only — hot keys no
         # longer serialize per-occurrence atomics)
         inverse, counts, rank = self._dedup_count(
-            occ_entry, values_cat.numel(),
-            pad_keys=values_cat if pad else None)
+            occ_entry, nnz, pad_keys=values_cat if pad else None,
+            counts=counts)
         slots = self._dedup_admit(centry_buf, uniq_buf, counts,
                                   m_dev=m_counter)
         return DedupResult(uniq_buf, inverse, counts, slots, rank, m_counter)
+
+    def dedup_lookup_capture_matrix(self, ids: torch.Tensor,
+                                    bump_step=True) -> DedupResult:
+        """dedup_lookup_capture for the one-id-per-table layout: ids is
+        [batch, n_tables] (int64, contiguous) and the composite keys
+        ids[b, t] + (t << key_bits), in occurrence order t * batch + b, are
+        never materialised."""
+        return self.dedup_lookup_capture(ids, bump_step=bump_step,
+                                         matrix=True)
 
     def dedup_only_capture(self, values_cat: torch.Tensor) -> DedupResult:
         """Requester-side dedup for the padded sharded exchange: claim-only

@@ -352,7 +352,7 @@ class _PaddedShardedLookup(torch.autograd.Function):
             grad_own.index_add_(0, ex.own_inv, grad_recv)
             grad_own = grad_own[:n_own]
         coll.accumulate_grad(ex.own_slots, ex.own_keys, grad_own)
-        return (torch.zeros_like(coll._anchor),) + (None,) * 11
+        return (None,) * 12
 
 
 def _a2a(sev: ShardedEmbeddingCollection, tensor, in_sp, out_sp):
@@ -441,4 +441,4 @@ class _ShardedCollectionLookup(torch.autograd.Function):
                             device=grad_recv.device, dtype=grad_recv.dtype)
         grad2.index_add_(0, inv2.long(), grad_recv)
         coll.accumulate_grad(slots2, uniq2, grad2)
-        return (torch.zeros_like(coll._anchor),) + (None,) * 12
+        return (None,) * 13

@@ -156,7 +156,7 @@ class _ShardedPooledLookup(torch.autograd.Function):
                             device=grad_recv.device, dtype=grad_recv.dtype)
         grad2.index_add_(0, inv2, grad_recv)
         sev.local_ev.accumulate_grad(slots2, uniq2, grad2)
-        return (torch.zeros_like(sev.local_ev._anchor),) + (None,) * 9
+        return (None,) * 10
 
 
 def _sharded_lookup_infer(sev: ShardedEmbeddingVariable, uniq, inverse,
