@@ -19,11 +19,11 @@ _EXT_NAME = "deeprec_amd_hip"
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _EXT_DIR = os.path.normpath(os.path.join(_HERE, "..", "_ext"))
 _SOURCES = [os.path.join(_HERE, "hip", "ev_kernels.hip"),
+            os.path.join(_HERE, "hip", "ev_read_kernels.hip"),
             os.path.join(_HERE, "hip", "dense_kernels.hip"),
             os.path.join(_HERE, "hip", "gru_kernels.hip"),
             os.path.join(_HERE, "hip", "attention_kernels.hip"),
             os.path.join(_HERE, "hip", "fp8_kernels.hip"),
-            os.path.join(_HERE, "hip", "quant_ev_kernels.hip"),
             os.path.join(_HERE, "hip", "loss_kernels.hip")]
 _HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 _ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")

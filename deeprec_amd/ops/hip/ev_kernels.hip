@@ -44,7 +44,6 @@ DEV_INLINE uint64_t mix_hash(uint64_t k) {
 }
 
 DEV_INLINE float bf2f(__hip_bfloat16 v) { return __bfloat162float(v); }
-DEV_INLINE __hip_bfloat16 f2bf(float v) { return __float2bfloat16(v); }
 
 // ---------------------------------------------------------------------
 // hash probe / insert
@@ -851,173 +850,8 @@ __global__ void k_export_scan(
 }
 
 // ---------------------------------------------------------------------
-// gather / pooled forward / pooled backward
+// pooled backward (the forward read kernels are in ev_read_kernels.hip)
 // ---------------------------------------------------------------------
-
-// Plain gather of unique rows: out[i] = values[slots[i]] or default row.
-template <typename OutT>
-__global__ void k_gather(
-    const float* __restrict__ values, const float* __restrict__ default_values,
-    const int64_t* __restrict__ keys, const int32_t* __restrict__ slots,
-    int m, int dim, int default_value_dim, float no_permission_value,
-    int use_no_permission, OutT* __restrict__ out) {
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)m * dim;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; t < total; t += stride) {
-    int i = (int)(t / dim);
-    int d = (int)(t % dim);
-    int32_t s = slots[i];
-    float v;
-    if (s >= 0) {
-      v = values[(int64_t)s * dim + d];
-    } else if (use_no_permission) {
-      v = no_permission_value;
-    } else {
-      int64_t row = (int64_t)((uint64_t)keys[i] % (uint64_t)default_value_dim);
-      v = default_values[row * dim + d];
-    }
-    if constexpr (std::is_same_v<OutT, __hip_bfloat16>) out[t] = f2bf(v);
-    else out[t] = v;
-  }
-}
-
-// Unpooled gather over a padded stream (sequence features):
-//   out[j, :] = 0                        where inverse[j] < 0 (padding)
-//   out[j, :] = row of slots[inverse[j]] otherwise, with k_gather's
-//               default-row / no-permission handling for slot < 0.
-// slots/keys may be nnz-padded (capture): only rows a valid inverse names
-// are read, and an inverse past n_uniq is treated as padding, never
-// dereferenced. Memory-bound on the [nnz, dim] write: a thread moves VEC
-// consecutive elements (VEC * sizeof(OutT) = 16 B when dim allows it) and
-// consecutive threads take consecutive chunks of a row, so a wave writes
-// whole rows back to back. VEC == 1 is the scalar path for any dim.
-template <typename OutT, int VEC>
-__global__ void k_seq_gather_pad(
-    const float* __restrict__ values, const float* __restrict__ default_values,
-    const int64_t* __restrict__ keys, const int32_t* __restrict__ slots,
-    const int32_t* __restrict__ inverse, int nnz, int n_uniq, int dim,
-    int default_value_dim, float no_permission_value, int use_no_permission,
-    OutT* __restrict__ out) {
-  const int cpr = dim / VEC;  // chunks per row
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  const int64_t total = (int64_t)nnz * cpr;
-  const int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; t < total; t += stride) {
-    const int j = (int)(t / cpr);
-    const int d0 = (int)(t % cpr) * VEC;
-    const int u = inverse[j];
-    float v[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) v[i] = 0.0f;
-    if ((unsigned)u < (unsigned)n_uniq) {
-      const int32_t s = slots[u];
-      const float* src = nullptr;
-      if (s >= 0) {
-        src = values + (int64_t)s * dim + d0;
-      } else if (!use_no_permission) {
-        int64_t row =
-            (int64_t)((uint64_t)keys[u] % (uint64_t)default_value_dim);
-        src = default_values + row * dim + d0;
-      }
-      if (src) {
-        if constexpr (VEC % 4 == 0) {  // rows are 16-B aligned: dim % 4 == 0
-#pragma unroll
-          for (int i = 0; i < VEC; i += 4) {
-            const float4 q = *reinterpret_cast<const float4*>(src + i);
-            v[i] = q.x; v[i + 1] = q.y; v[i + 2] = q.z; v[i + 3] = q.w;
-          }
-        } else {
-#pragma unroll
-          for (int i = 0; i < VEC; ++i) v[i] = src[i];
-        }
-      } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) v[i] = no_permission_value;
-      }
-    }
-    OutT* dst = out + (int64_t)j * dim + d0;
-    if constexpr (std::is_same_v<OutT, __hip_bfloat16>) {
-      if constexpr (VEC == 1) {
-        dst[0] = f2bf(v[0]);
-      } else {
-        // pack pairs of bf16 into 32-bit words: one 8- or 16-byte store
-        uint32_t w[VEC / 2];
-#pragma unroll
-        for (int i = 0; i < VEC / 2; ++i) {
-          const __hip_bfloat16 lo = f2bf(v[2 * i]), hi = f2bf(v[2 * i + 1]);
-          w[i] = (uint32_t)(*reinterpret_cast<const uint16_t*>(&lo)) |
-                 ((uint32_t)(*reinterpret_cast<const uint16_t*>(&hi)) << 16);
-        }
-        if constexpr (VEC == 8)
-          *reinterpret_cast<uint4*>(dst) = make_uint4(w[0], w[1], w[2], w[3]);
-        else
-          *reinterpret_cast<uint2*>(dst) = make_uint2(w[0], w[1]);
-      }
-    } else {
-      if constexpr (VEC == 4)
-        *reinterpret_cast<float4*>(dst) = make_float4(v[0], v[1], v[2], v[3]);
-      else
-        dst[0] = v[0];
-    }
-  }
-}
-
-DEV_INLINE float row_coeff(int combiner, int len, const float* wsum) {
-  // combiner: 0=sum 1=mean 2=sqrtn; wsum = sum w (mean) / sum w^2 (sqrtn)
-  if (combiner == 0 || len == 0) return 1.0f;
-  float denom = wsum ? *wsum : (float)len;
-  if (combiner == 2) denom = sqrtf(wsum ? *wsum : (float)len);
-  return denom > 1e-12f ? 1.0f / denom : 0.0f;
-}
-
-// Fused gather + segment pooling. Thread = (batch row b, dim d); loops the
-// row's ids accumulating values[slots[inverse[j]]][d]. No [nnz, dim] or
-// [m, dim] intermediate is materialized.
-template <typename OutT>
-__global__ void k_pooled_fwd(
-    const float* __restrict__ values, const float* __restrict__ default_values,
-    const int64_t* __restrict__ keys, const int32_t* __restrict__ slots,
-    const int32_t* __restrict__ inverse, const int32_t* __restrict__ offsets,
-    const float* __restrict__ weights, int batch, int dim,
-    int default_value_dim, float no_permission_value, int use_no_permission,
-    int combiner, OutT* __restrict__ out) {
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)batch * dim;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; t < total; t += stride) {
-    int b = (int)(t / dim);
-    int d = (int)(t % dim);
-    int beg = offsets[b], end = offsets[b + 1];
-    float acc = 0.0f, wacc = 0.0f;
-    for (int j = beg; j < end; ++j) {
-      int u = inverse[j];
-      int32_t s = slots[u];
-      float v;
-      if (s >= 0) {
-        v = values[(int64_t)s * dim + d];
-      } else if (use_no_permission) {
-        v = no_permission_value;
-      } else {
-        int64_t row =
-            (int64_t)((uint64_t)keys[u] % (uint64_t)default_value_dim);
-        v = default_values[row * dim + d];
-      }
-      float w = weights ? weights[j] : 1.0f;
-      acc += w * v;
-      wacc += (combiner == 2) ? w * w : w;
-    }
-    float coeff = 1.0f;
-    int len = end - beg;
-    if (combiner != 0 && len > 0) {
-      float denom = (combiner == 2) ? sqrtf(wacc) : wacc;
-      coeff = denom > 1e-12f ? 1.0f / denom : 0.0f;
-    }
-    float r = acc * coeff;
-    if constexpr (std::is_same_v<OutT, __hip_bfloat16>) out[t] = f2bf(r);
-    else out[t] = r;
-  }
-}
 
 // Pooled backward: grad_unique[u][d] += coeff(b) * w_j * grad_out[b][d]
 // for every occurrence j of unique key u. Thread = (b, d); atomicAdd into
@@ -1060,7 +894,7 @@ __global__ void k_pooled_bwd(
 }
 
 // ---------------------------------------------------------------------
-// grouped (multi-table) fused pooling — the EmbeddingCollection hot path
+// grouped (multi-table) pooled backward — the EmbeddingCollection hot path
 // ---------------------------------------------------------------------
 //
 // N tables of equal dim share one storage via composite keys
@@ -1071,68 +905,9 @@ __global__ void k_pooled_bwd(
 //
 // Ragged layout: the N tables' ragged batches are concatenated —
 // offsets[(N*B)+1]; pooled row r (< N*B) is table t = r / B, sample
-// b = r % B. Output is written interleaved as out[b, t*D + d] giving the
-// [B, N*D] concat layout models consume with no extra copy.
-
-// direct != nullptr (sharded path): embedding rows come pre-gathered per
-// unique key (from peer shards over RCCL all-to-all) instead of the local
-// slot slab.
-template <typename OutT>
-__global__ void k_group_pooled_fwd(
-    const float* __restrict__ values, const float* __restrict__ default_values,
-    const int64_t* __restrict__ keys, const int32_t* __restrict__ slots,
-    const int32_t* __restrict__ inverse, const int32_t* __restrict__ offsets,
-    const float* __restrict__ weights,
-    const int32_t* __restrict__ combiner_ids, int batch, int n_tables,
-    int dim, int default_value_dim, int key_bits, float no_permission_value,
-    int use_no_permission, const float* __restrict__ direct,
-    OutT* __restrict__ out) {
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t total = (int64_t)batch * n_tables * dim;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  const int64_t key_mask = ((int64_t)1 << key_bits) - 1;
-  for (; t < total; t += stride) {
-    int d = (int)(t % dim);
-    int64_t rid = t / dim;           // pooled row in [0, N*B)
-    int table = (int)(rid / batch);
-    int b = (int)(rid % batch);
-    int beg = offsets[rid], end = offsets[rid + 1];
-    int combiner = combiner_ids[table];
-    float acc = 0.0f, wacc = 0.0f;
-    for (int j = beg; j < end; ++j) {
-      int u = inverse[j];
-      float v;
-      if (direct) {
-        v = direct[(int64_t)u * dim + d];
-      } else {
-        int32_t s = slots[u];
-        if (s >= 0) {
-          v = values[(int64_t)s * dim + d];
-        } else if (use_no_permission) {
-          v = no_permission_value;
-        } else {
-          int64_t k = keys[u];
-          int64_t row = (int64_t)(table)*default_value_dim +
-                        (int64_t)((uint64_t)(k & key_mask) %
-                                  (uint64_t)default_value_dim);
-          v = default_values[row * dim + d];
-        }
-      }
-      float w = weights ? weights[j] : 1.0f;
-      acc += w * v;
-      wacc += (combiner == 2) ? w * w : w;
-    }
-    float coeff = 1.0f;
-    if (combiner != 0 && end > beg) {
-      float denom = (combiner == 2) ? sqrtf(wacc) : wacc;
-      coeff = denom > 1e-12f ? 1.0f / denom : 0.0f;
-    }
-    float r = acc * coeff;
-    int64_t oidx = ((int64_t)b * n_tables + table) * dim + d;
-    if constexpr (std::is_same_v<OutT, __hip_bfloat16>) out[oidx] = f2bf(r);
-    else out[oidx] = r;
-  }
-}
+// b = r % B. The forward (k_group_pooled_fwd, ev_read_kernels.hip) writes
+// its output interleaved as out[b, t*D + d], the [B, N*D] concat layout
+// models consume with no extra copy; grad_out arrives in that layout.
 
 // Balanced segmented grad scatter. Work is split over OCCURRENCES in
 // sorted (CSR) order, not over unique keys: a group of LANES lanes (one
@@ -1773,68 +1548,6 @@ torch::Tensor csr_scatter_pad(torch::Tensor inverse, torch::Tensor rank,
   return order;
 }
 
-template <typename OutT, int VEC>
-static void launch_seq_gather_pad(
-    torch::Tensor& values, torch::Tensor& default_values, torch::Tensor& keys,
-    torch::Tensor& slots, torch::Tensor& inverse, int dim,
-    double no_permission_value, bool use_no_permission, OutT* out,
-    hipStream_t stream) {
-  int64_t nnz = inverse.numel();
-  k_seq_gather_pad<OutT, VEC>
-      <<<n_blocks(nnz * (dim / VEC)), kBlock, 0, stream>>>(
-          values.data_ptr<float>(), default_values.data_ptr<float>(),
-          keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
-          inverse.data_ptr<int32_t>(), (int)nnz, (int)slots.numel(), dim,
-          (int)default_values.size(0), (float)no_permission_value,
-          use_no_permission ? 1 : 0, out);
-}
-
-// out [nnz, dim]: zero rows where inverse < 0, else the row of
-// slots[inverse] (see k_seq_gather_pad). keys/slots may be nnz-padded.
-torch::Tensor seq_gather_pad(torch::Tensor values,
-                             torch::Tensor default_values, torch::Tensor keys,
-                             torch::Tensor slots, torch::Tensor inverse,
-                             double no_permission_value,
-                             bool use_no_permission,
-                             torch::ScalarType out_dtype) {
-  CHECK_DEV(inverse);
-  TORCH_CHECK(keys.numel() == slots.numel(),
-              "seq_gather_pad: keys/slots size mismatch");
-  TORCH_CHECK(out_dtype == torch::kFloat32 || out_dtype == torch::kBFloat16,
-              "seq_gather_pad: out dtype must be float32 or bfloat16");
-  int64_t nnz = inverse.numel();
-  int dim = values.size(1);
-  auto out = torch::empty({nnz, dim}, values.options().dtype(out_dtype));
-  if (nnz * dim == 0) return out;
-  auto stream = current_hip_stream();
-  if (out_dtype == torch::kBFloat16) {
-    auto* op = reinterpret_cast<__hip_bfloat16*>(out.data_ptr<at::BFloat16>());
-    if (dim % 8 == 0)
-      launch_seq_gather_pad<__hip_bfloat16, 8>(
-          values, default_values, keys, slots, inverse, dim,
-          no_permission_value, use_no_permission, op, stream);
-    else if (dim % 4 == 0)
-      launch_seq_gather_pad<__hip_bfloat16, 4>(
-          values, default_values, keys, slots, inverse, dim,
-          no_permission_value, use_no_permission, op, stream);
-    else
-      launch_seq_gather_pad<__hip_bfloat16, 1>(
-          values, default_values, keys, slots, inverse, dim,
-          no_permission_value, use_no_permission, op, stream);
-  } else {
-    auto* op = out.data_ptr<float>();
-    if (dim % 4 == 0)
-      launch_seq_gather_pad<float, 4>(
-          values, default_values, keys, slots, inverse, dim,
-          no_permission_value, use_no_permission, op, stream);
-    else
-      launch_seq_gather_pad<float, 1>(
-          values, default_values, keys, slots, inverse, dim,
-          no_permission_value, use_no_permission, op, stream);
-  }
-  return out;
-}
-
 torch::Tensor csr_order(torch::Tensor inverse, torch::Tensor bounds,
                         int64_t m) {
   int64_t nnz = inverse.numel();
@@ -1909,67 +1622,6 @@ ht_export(torch::Tensor ht_keys, torch::Tensor ht_slot, torch::Tensor ht_freq,
   return {out_keys, out_slots, out_freqs, out_versions};
 }
 
-torch::Tensor ev_gather(torch::Tensor values, torch::Tensor default_values,
-                        torch::Tensor keys, torch::Tensor slots,
-                        double no_permission_value, bool use_no_permission,
-                        torch::ScalarType out_dtype) {
-  int m = keys.numel();
-  int dim = values.size(1);
-  auto out = torch::empty({m, dim}, values.options().dtype(out_dtype));
-  if (m == 0) return out;
-  auto stream = current_hip_stream();
-  int64_t total = (int64_t)m * dim;
-  if (out_dtype == torch::kBFloat16) {
-    k_gather<__hip_bfloat16><<<n_blocks(total), kBlock, 0, stream>>>(
-        values.data_ptr<float>(), default_values.data_ptr<float>(),
-        keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(), m, dim,
-        default_values.size(0), (float)no_permission_value,
-        use_no_permission ? 1 : 0,
-        reinterpret_cast<__hip_bfloat16*>(out.data_ptr<at::BFloat16>()));
-  } else {
-    k_gather<float><<<n_blocks(total), kBlock, 0, stream>>>(
-        values.data_ptr<float>(), default_values.data_ptr<float>(),
-        keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(), m, dim,
-        default_values.size(0), (float)no_permission_value,
-        use_no_permission ? 1 : 0, out.data_ptr<float>());
-  }
-  return out;
-}
-
-torch::Tensor pooled_fwd(torch::Tensor values, torch::Tensor default_values,
-                         torch::Tensor keys, torch::Tensor slots,
-                         torch::Tensor inverse, torch::Tensor offsets,
-                         torch::Tensor weights, int64_t combiner,
-                         double no_permission_value, bool use_no_permission,
-                         torch::ScalarType out_dtype) {
-  int batch = offsets.numel() - 1;
-  int dim = values.size(1);
-  auto out = torch::empty({batch, dim}, values.options().dtype(out_dtype));
-  if (batch == 0) return out;
-  auto stream = current_hip_stream();
-  int64_t total = (int64_t)batch * dim;
-  const float* wptr =
-      weights.defined() && weights.numel() ? weights.data_ptr<float>()
-                                           : nullptr;
-  if (out_dtype == torch::kBFloat16) {
-    k_pooled_fwd<__hip_bfloat16><<<n_blocks(total), kBlock, 0, stream>>>(
-        values.data_ptr<float>(), default_values.data_ptr<float>(),
-        keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
-        inverse.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(), wptr, batch,
-        dim, default_values.size(0), (float)no_permission_value,
-        use_no_permission ? 1 : 0, (int)combiner,
-        reinterpret_cast<__hip_bfloat16*>(out.data_ptr<at::BFloat16>()));
-  } else {
-    k_pooled_fwd<float><<<n_blocks(total), kBlock, 0, stream>>>(
-        values.data_ptr<float>(), default_values.data_ptr<float>(),
-        keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
-        inverse.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(), wptr, batch,
-        dim, default_values.size(0), (float)no_permission_value,
-        use_no_permission ? 1 : 0, (int)combiner, out.data_ptr<float>());
-  }
-  return out;
-}
-
 torch::Tensor pooled_bwd(torch::Tensor grad_out, torch::Tensor inverse,
                          torch::Tensor offsets, torch::Tensor weights,
                          int64_t m, int64_t combiner) {
@@ -1996,75 +1648,6 @@ torch::Tensor pooled_bwd(torch::Tensor grad_out, torch::Tensor inverse,
         grad_unique.data_ptr<float>());
   }
   return grad_unique;
-}
-
-torch::Tensor group_pooled_fwd(
-    torch::Tensor values, torch::Tensor default_values, torch::Tensor keys,
-    torch::Tensor slots, torch::Tensor inverse, torch::Tensor offsets,
-    torch::Tensor weights, torch::Tensor combiner_ids, int64_t batch,
-    int64_t n_tables, int64_t key_bits, double no_permission_value,
-    bool use_no_permission, torch::ScalarType out_dtype) {
-  int dim = values.size(1);
-  auto out = torch::empty({batch, n_tables * dim},
-                          values.options().dtype(out_dtype));
-  int64_t total = batch * n_tables * dim;
-  if (total == 0) return out;
-  auto stream = current_hip_stream();
-  const float* wptr =
-      weights.defined() && weights.numel() ? weights.data_ptr<float>()
-                                           : nullptr;
-  if (out_dtype == torch::kBFloat16) {
-    k_group_pooled_fwd<__hip_bfloat16>
-        <<<n_blocks(total), kBlock, 0, stream>>>(
-            values.data_ptr<float>(), default_values.data_ptr<float>(),
-            keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
-            inverse.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(), wptr,
-            combiner_ids.data_ptr<int32_t>(), (int)batch, (int)n_tables, dim,
-            default_values.size(0) / (int)n_tables, (int)key_bits,
-            (float)no_permission_value, use_no_permission ? 1 : 0, nullptr,
-            reinterpret_cast<__hip_bfloat16*>(out.data_ptr<at::BFloat16>()));
-  } else {
-    k_group_pooled_fwd<float><<<n_blocks(total), kBlock, 0, stream>>>(
-        values.data_ptr<float>(), default_values.data_ptr<float>(),
-        keys.data_ptr<int64_t>(), slots.data_ptr<int32_t>(),
-        inverse.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(), wptr,
-        combiner_ids.data_ptr<int32_t>(), (int)batch, (int)n_tables, dim,
-        default_values.size(0) / (int)n_tables, (int)key_bits,
-        (float)no_permission_value, use_no_permission ? 1 : 0, nullptr,
-        out.data_ptr<float>());
-  }
-  return out;
-}
-
-torch::Tensor group_pooled_fwd_direct(
-    torch::Tensor emb_rows, torch::Tensor keys, torch::Tensor inverse,
-    torch::Tensor offsets, torch::Tensor weights, torch::Tensor combiner_ids,
-    int64_t batch, int64_t n_tables, torch::ScalarType out_dtype) {
-  int dim = emb_rows.size(1);
-  auto out = torch::empty({batch, n_tables * dim},
-                          emb_rows.options().dtype(out_dtype));
-  int64_t total = batch * n_tables * dim;
-  if (total == 0) return out;
-  auto stream = current_hip_stream();
-  const float* wptr =
-      weights.defined() && weights.numel() ? weights.data_ptr<float>()
-                                           : nullptr;
-  if (out_dtype == torch::kBFloat16) {
-    k_group_pooled_fwd<__hip_bfloat16>
-        <<<n_blocks(total), kBlock, 0, stream>>>(
-            nullptr, nullptr, keys.data_ptr<int64_t>(), nullptr,
-            inverse.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(), wptr,
-            combiner_ids.data_ptr<int32_t>(), (int)batch, (int)n_tables, dim,
-            1, 0, 0.0f, 0, emb_rows.data_ptr<float>(),
-            reinterpret_cast<__hip_bfloat16*>(out.data_ptr<at::BFloat16>()));
-  } else {
-    k_group_pooled_fwd<float><<<n_blocks(total), kBlock, 0, stream>>>(
-        nullptr, nullptr, keys.data_ptr<int64_t>(), nullptr,
-        inverse.data_ptr<int32_t>(), offsets.data_ptr<int32_t>(), wptr,
-        combiner_ids.data_ptr<int32_t>(), (int)batch, (int)n_tables, dim, 1,
-        0, 0.0f, 0, emb_rows.data_ptr<float>(), out.data_ptr<float>());
-  }
-  return out;
 }
 
 // Positions of `order` per lane group in k_group_pooled_bwd_seg. From the
@@ -2300,7 +1883,7 @@ void register_dense(pybind11::module_& mod);      // dense_kernels.hip
 void register_gru(pybind11::module_& mod);        // gru_kernels.hip
 void register_attention(pybind11::module_& mod);  // attention_kernels.hip
 void register_fp8(pybind11::module_& mod);        // fp8_kernels.hip
-void register_quant_ev(pybind11::module_& mod);   // quant_ev_kernels.hip
+void register_ev_read(pybind11::module_& mod);    // ev_read_kernels.hip
 void register_loss(pybind11::module_& mod);       // loss_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -2308,7 +1891,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_gru(mod);
   register_attention(mod);
   register_fp8(mod);
-  register_quant_ev(mod);
+  register_ev_read(mod);
   register_loss(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
@@ -2335,15 +1918,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("csr_order", &csr_order);
   mod.def("csr_scatter", &csr_scatter);
   mod.def("csr_scatter_pad", &csr_scatter_pad);
-  mod.def("seq_gather_pad", &seq_gather_pad);
   mod.def("ht_insert_bulk", &ht_insert_bulk);
   mod.def("ht_lookup", &ht_lookup);
   mod.def("ht_export", &ht_export);
-  mod.def("ev_gather", &ev_gather);
-  mod.def("pooled_fwd", &pooled_fwd);
   mod.def("pooled_bwd", &pooled_bwd);
-  mod.def("group_pooled_fwd", &group_pooled_fwd);
-  mod.def("group_pooled_fwd_direct", &group_pooled_fwd_direct);
   mod.def("group_pooled_bwd_seg", &group_pooled_bwd_seg);
   mod.attr("BWD_SEG_R") = (int64_t)kSegR;
   mod.def("apply_sgd", &apply_sgd);

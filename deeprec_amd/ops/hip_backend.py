@@ -1,8 +1,9 @@
 """HBM (GPU) storage backend: Python wrapper over the HIP embedding engine.
 
 Same interface/semantics as ops/cpu_backend.CpuStorage; all hot-path work
-runs in the hand-written gfx950 kernels (ops/hip/ev_kernels.hip). Growth
-and shrink/compaction are host-coordinated (rare, off the hot path) —
+runs in the hand-written gfx950 kernels (ops/hip/ev_kernels.hip; the
+gather / pooled-forward reads in ops/hip/ev_read_kernels.hip). Growth and
+shrink/compaction are host-coordinated (rare, off the hot path) —
 mirroring the reference's coarse multi-tier design choice (SURVEY.md §7
 hard parts: host-coordinated rehash).
 """

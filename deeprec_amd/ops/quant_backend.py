@@ -3,7 +3,7 @@ is OCP e4m3 bytes with one fp32 scale per row.
 
 Rows cost dim + 4 bytes instead of 4 * dim (20 B instead of 64 B at dim
 16) and are dequantized inside the gather/pool kernels
-(ops/hip/quant_ev_kernels.hip): value(s, d) = fl32(scale[s] *
+(Q8Rows, ops/hip/ev_read_kernels.hip): value(s, d) = fl32(scale[s] *
 decode_e4m3(q[s, d])), exactly ops/fp8.dequantize_fp8_rows. The hash table,
 admission metadata and default_values (fp32, small) are HbmStorage's own.
 Quantization is the per-row scheme of ops/fp8.py (scale = amax/448, 1 for

@@ -1,17 +1,21 @@
 """fp8-resident embedding storage (ops/quant_backend.py) and its
-dequantizing read kernels (ops/hip/quant_ev_kernels.hip).
+dequantizing read kernels (Q8Rows in ops/hip/ev_read_kernels.hip).
 
 Semantics under test: value(s, d) = fl32(scale[s] * decode_e4m3(q[s, d])),
 which is ops.fp8.dequantize_fp8_rows, so every gather is compared exactly
 (`torch.equal`) against that function on the CPU. Pooling accumulates in
 fp32 in bag order, applies the combiner coefficient and rounds once; its
-bound against a float64 pool is derived below, not tuned. Bytes and scales
+bound against a float64 pool is derived (tests/read_reference.py), not tuned. Bytes and scales
 are asymmetric random values so a swapped byte order inside a 32-bit word
 or a scale applied to the wrong row cannot cancel. 0x7F / 0xFF (the two
 e4m3 NaN codes) never occur: neither the quantizer nor anything here emits
 them."""
 import pytest
 import torch
+
+from tests.read_reference import IDS_PER_TABLE, bags
+from tests.read_reference import check_pool as _check_pool
+from tests.read_reference import pool_reference as _pool_reference
 
 pytestmark = pytest.mark.gpu
 
@@ -143,69 +147,16 @@ def test_seq_gather_pad_is_exact(dim, no_permission):
 # 3. pooled and group pooled
 # --------------------------------------------------------------------------
 #
-# The kernel computes, per output element, acc = sum_j fl(w_j * v_j) in
-# fp32 in j order (L products, L - 1 sums that matter), then fl(acc *
-# coeff) with coeff one or two fp32 operations on the weight sum. Each
-# rounding is at most 2^-24 relative to a partial result bounded by
-# sum_j |w_j v_j|, which gives, to first order,
-#     |out - ref| <= (L + 2) * 2^-24 * coeff * sum_j |w_j v_j|.
-# A bf16 output adds one more rounding: 2^-8 * |ref| (2^-9 half-ulp plus the
-# fp32 error above moving the rounding point; 2^-8 covers both).
+# The bound, derived in tests/read_reference.py:
+#     |out - ref| <= (L + 2) * 2^-24 * coeff * sum_j |w_j v_j|,
+# plus 2^-8 * |ref| for a bf16 output.
 
 BATCH, N_TABLES = 7, 3
 COMBINERS = ["sum", "mean", "sqrtn"]
-IDS_PER_TABLE = 40     # ids 0..39 are imported; 40..44 are missing keys
 
 
 def _bags(gen, weighted, n_rows):
-    from deeprec_amd.embedding.ragged import RaggedIds
-    lengths = torch.randint(0, 6, (n_rows,), generator=gen)
-    lengths[0], lengths[1] = 0, 5        # an empty bag and a full one
-    offsets = torch.zeros(n_rows + 1, dtype=torch.int32)
-    offsets[1:] = lengths.cumsum(0)
-    nnz = int(offsets[-1])
-    ids = torch.randint(0, IDS_PER_TABLE + 5, (nnz,), generator=gen)
-    ids[0] = IDS_PER_TABLE + 1           # at least one missing key
-    w =(torch.rand(nnz, generator=gen) + 0.5) if weighted else None
-    return RaggedIds(ids.to(DEV), offsets.to(DEV),
-                     w.to(DEV) if weighted else None), ids, offsets, w
-
-
-def _pool_reference(rows_of, ids, offsets, w, combiner):
-    """float64 pool over the dequantized rows: (ref, bound term
-    coeff * sum |w v|, bag length), each [n_rows, dim] / [n_rows]."""
-    n_rows = offsets.numel() - 1
-    dim = rows_of(ids[:0]).shape[1]
-    ref = torch.zeros(n_rows, dim, dtype=torch.float64)
-    mag = torch.zeros(n_rows, dim, dtype=torch.float64)
-    lens = torch.zeros(n_rows, dtype=torch.float64)
-    for r in range(n_rows):
-        lo, hi = int(offsets[r]), int(offsets[r + 1])
-        if hi == lo:
-            continue
-        v = rows_of(ids[lo:hi]).double()
-        wj = (w[lo:hi].double() if w is not None
-              else torch.ones(hi - lo, dtype=torch.float64))
-        if combiner == "sum":
-            coeff = 1.0
-        elif combiner == "mean":
-            coeff = 1.0 / float(wj.sum())
-        else:
-            coeff = 1.0 / float((wj * wj).sum().sqrt())
-        ref[r] = (wj[:, None] * v).sum(0) * coeff
-        mag[r] = (wj[:, None] * v).abs().sum(0) * coeff
-        lens[r] = hi - lo
-    return ref, mag, lens
-
-
-def _check_pool(out, ref, mag, lens, label):
-    bound = (lens[:, None] + 2) * 2.0 ** -24 * mag
-    if out.dtype == torch.bfloat16:
-        bound = bound + 2.0 ** -8 * ref.abs()
-    err = (out.cpu().double() - ref).abs()
-    worst = float((err / bound.clamp(min=1e-300)).max())
-    print(f"{label}: max err/bound = {worst:.3f}")
-    assert bool((err <= bound).all()), f"{label}: err/bound {worst:.3f}"
+    return bags(gen, weighted, n_rows, DEV)
 
 
 @pytest.mark.parametrize("weighted", [False, True], ids=["plain", "weighted"])
