@@ -29,11 +29,10 @@ from typing import Dict, List, Optional
 import torch
 from safetensors.torch import load_file, save_file
 
-NUM_BUCKETS = 1000  # reference kSavedPartitionNum
+# the optimizer slabs we persist when present
+from deeprec_amd.ops.common import SLAB_NAMES as _SLAB_NAMES
 
-# optimizer slab names we persist when present
-_SLAB_NAMES = ["adagrad_accum", "adagrad_decay_period", "adam_m", "adam_v",
-               "ftrl_accum", "ftrl_linear"]
+NUM_BUCKETS = 1000  # reference kSavedPartitionNum
 
 
 def _is_collection(ev) -> bool:

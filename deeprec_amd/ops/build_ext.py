@@ -20,6 +20,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _EXT_DIR = os.path.normpath(os.path.join(_HERE, "..", "_ext"))
 _SOURCES = [os.path.join(_HERE, "hip", "ev_kernels.hip"),
             os.path.join(_HERE, "hip", "ev_read_kernels.hip"),
+            os.path.join(_HERE, "hip", "ev_apply_kernels.hip"),
             os.path.join(_HERE, "hip", "dense_kernels.hip"),
             os.path.join(_HERE, "hip", "gru_kernels.hip"),
             os.path.join(_HERE, "hip", "attention_kernels.hip"),

@@ -18,7 +18,8 @@
 //   - grad scatter ≙ DoEmbeddingGrad/DistributeGradToShard
 //   - sparse optimizer applies ≙ training_ali_ops_gpu.cu.cc kernels,
 //     operating directly on slot indices from the step's single probe
-//     (the reference's `_OPT_` indices-as-pointers fusion).
+//     (the reference's `_OPT_` indices-as-pointers fusion); they live in
+//     ev_apply_kernels.hip.
 //
 // CDNA4 notes: wavefront = 64; all elementwise kernels use a (row, dim)
 // thread mapping with grid-stride so consecutive lanes read consecutive
@@ -997,176 +998,6 @@ __global__ void k_group_pooled_bwd_seg(
   }
 }
 
-// ---------------------------------------------------------------------
-// fused sparse optimizer applies (thread = (unique key i, dim d))
-// ---------------------------------------------------------------------
-
-#define APPLY_PROLOG                                              \
-  int64_t t = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;     \
-  int64_t total = (int64_t)m * dim;                               \
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;               \
-  for (; t < total; t += stride) {                                \
-    int i = (int)(t / dim);                                       \
-    int d = (int)(t % dim);                                       \
-    int32_t s = slots[i];                                         \
-    if (s < 0) continue;                                          \
-    int64_t o = (int64_t)s * dim + d;                             \
-    float g = grad[t];
-
-#define APPLY_EPILOG }
-
-__global__ void k_apply_sgd(float* __restrict__ w,
-                            const int32_t* __restrict__ slots,
-                            const float* __restrict__ grad, int m, int dim,
-                            float lr) {
-  APPLY_PROLOG
-  w[o] -= lr * g;
-  APPLY_EPILOG
-}
-
-__global__ void k_apply_adagrad(float* __restrict__ w,
-                                float* __restrict__ accum,
-                                const int32_t* __restrict__ slots,
-                                const float* __restrict__ grad, int m,
-                                int dim, float lr, float epsilon) {
-  APPLY_PROLOG
-  float a = accum[o] + g * g;
-  accum[o] = a;
-  w[o] -= lr * g / (sqrtf(a) + epsilon);
-  APPLY_EPILOG
-}
-
-// Periodic accumulator decay; period bookkeeping is per-slot (1-wide slab).
-// Lane d==0 updates the period after all lanes read it — benign ordering:
-// every thread computes the same decay from the pre-update period value
-// because the period slab is read before any write (separate arrays).
-__global__ void k_apply_adagrad_decay(
-    float* __restrict__ w, float* __restrict__ accum,
-    float* __restrict__ period_slab, const int32_t* __restrict__ slots,
-    const float* __restrict__ grad, int m, int dim, float lr, float epsilon,
-    float cur_period, float decay_rate, float baseline) {
-  APPLY_PROLOG
-  float prev_period = period_slab[s];
-  float dp = cur_period - prev_period;
-  if (dp < 0.0f) dp = 0.0f;
-  float decay = powf(decay_rate, dp);
-  float a = accum[o] * decay;
-  if (a < baseline) a = baseline;
-  a += g * g;
-  accum[o] = a;
-  w[o] -= lr * g / (sqrtf(a) + epsilon);
-  APPLY_EPILOG
-  // period_slab is committed by a separate k_commit_period launch so every
-  // (key, d) thread here reads the pre-update period value.
-}
-
-__global__ void k_commit_period(float* __restrict__ period_slab,
-                                const int32_t* __restrict__ slots, int m,
-                                float cur_period) {
-  int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t gstride = gridDim.x * (int64_t)blockDim.x;
-  for (; i < m; i += gstride) {
-    int32_t sl = slots[i];
-    if (sl >= 0) period_slab[sl] = cur_period;
-  }
-}
-
-__global__ void k_apply_adam(float* __restrict__ w, float* __restrict__ mom,
-                             float* __restrict__ vel,
-                             const int32_t* __restrict__ slots,
-                             const float* __restrict__ grad, int m, int dim,
-                             float lr_t, float beta1, float beta2,
-                             float epsilon) {
-  APPLY_PROLOG
-  float mn = beta1 * mom[o] + (1.0f - beta1) * g;
-  float vn = beta2 * vel[o] + (1.0f - beta2) * g * g;
-  mom[o] = mn;
-  vel[o] = vn;
-  w[o] -= lr_t * mn / (sqrtf(vn) + epsilon);
-  APPLY_EPILOG
-}
-
-__global__ void k_apply_adam_dev(float* __restrict__ w,
-                                 float* __restrict__ mom,
-                                 float* __restrict__ vel,
-                                 const int32_t* __restrict__ slots,
-                                 const float* __restrict__ grad, int m,
-                                 int dim, float lr, float beta1, float beta2,
-                                 float epsilon,
-                                 const float* __restrict__ powers) {
-  const float lr_t =
-      lr * sqrtf(1.0f - powers[1]) / (1.0f - powers[0]);
-  APPLY_PROLOG
-  float mn = beta1 * mom[o] + (1.0f - beta1) * g;
-  float vn = beta2 * vel[o] + (1.0f - beta2) * g * g;
-  mom[o] = mn;
-  vel[o] = vn;
-  w[o] -= lr_t * mn / (sqrtf(vn) + epsilon);
-  APPLY_EPILOG
-}
-
-__global__ void k_update_powers(float* __restrict__ powers, float beta1,
-                                float beta2) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) {
-    powers[0] *= beta1;
-    powers[1] *= beta2;
-  }
-}
-
-__global__ void k_apply_adamw(float* __restrict__ w, float* __restrict__ mom,
-                              float* __restrict__ vel,
-                              const int32_t* __restrict__ slots,
-                              const float* __restrict__ grad, int m, int dim,
-                              float lr_t, float lr, float beta1, float beta2,
-                              float epsilon, float weight_decay) {
-  APPLY_PROLOG
-  float mn = beta1 * mom[o] + (1.0f - beta1) * g;
-  float vn = beta2 * vel[o] + (1.0f - beta2) * g * g;
-  mom[o] = mn;
-  vel[o] = vn;
-  float wv = w[o];
-  w[o] = wv - lr_t * mn / (sqrtf(vn) + epsilon) - lr * weight_decay * wv;
-  APPLY_EPILOG
-}
-
-__global__ void k_apply_rmsprop(float* __restrict__ w, float* __restrict__ vel,
-                                const int32_t* __restrict__ slots,
-                                const float* __restrict__ grad, int m,
-                                int dim, float lr, float beta2,
-                                float epsilon) {
-  APPLY_PROLOG
-  float vn = beta2 * vel[o] + (1.0f - beta2) * g * g;
-  vel[o] = vn;
-  w[o] -= lr * g / (sqrtf(vn) + epsilon);
-  APPLY_EPILOG
-}
-
-// l2_shrinkage != 0 is the FtrlV2 variant (reference:
-// KvResourceSparseApplyFtrlV2): the linear term sees
-// g + 2*l2_shrinkage*w while the accumulator sees plain g^2.
-__global__ void k_apply_ftrl(float* __restrict__ w, float* __restrict__ n,
-                             float* __restrict__ z,
-                             const int32_t* __restrict__ slots,
-                             const float* __restrict__ grad, int m, int dim,
-                             float lr, float l1, float l2, float lr_power,
-                             float l2_shrinkage) {
-  APPLY_PROLOG
-  float wv = w[o];
-  float n_old = n[o];
-  float n_new = n_old + g * g;
-  float sigma = (powf(n_new, -lr_power) - powf(n_old, -lr_power)) / lr;
-  float gs = g + 2.0f * l2_shrinkage * wv;
-  float z_new = z[o] + gs - sigma * wv;
-  n[o] = n_new;
-  z[o] = z_new;
-  float quad = powf(n_new, -lr_power) / lr + 2.0f * l2;
-  float w_new = 0.0f;
-  if (fabsf(z_new) > l1)
-    w_new = ((z_new > 0.0f ? l1 : -l1) - z_new) / quad;
-  w[o] = w_new;
-  APPLY_EPILOG
-}
-
 }  // namespace
 
 // ---------------------------------------------------------------------
@@ -1761,129 +1592,12 @@ torch::Tensor group_pooled_bwd_seg(
   return grad_unique;
 }
 
-// ---------------- sparse applies ----------------
-
-void apply_sgd(torch::Tensor w, torch::Tensor slots, torch::Tensor grad,
-               double lr) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_sgd<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), slots.data_ptr<int32_t>(), grad.data_ptr<float>(),
-      m, dim, (float)lr);
-}
-
-void apply_adagrad(torch::Tensor w, torch::Tensor accum, torch::Tensor slots,
-                   torch::Tensor grad, double lr, double epsilon) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_adagrad<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), accum.data_ptr<float>(), slots.data_ptr<int32_t>(),
-      grad.data_ptr<float>(), m, dim, (float)lr, (float)epsilon);
-}
-
-void apply_adagrad_decay(torch::Tensor w, torch::Tensor accum,
-                         torch::Tensor period_slab, torch::Tensor slots,
-                         torch::Tensor grad, double lr, double epsilon,
-                         double cur_period, double decay_rate,
-                         double baseline) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_adagrad_decay<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), accum.data_ptr<float>(),
-      period_slab.data_ptr<float>(), slots.data_ptr<int32_t>(),
-      grad.data_ptr<float>(), m, dim, (float)lr, (float)epsilon,
-      (float)cur_period, (float)decay_rate, (float)baseline);
-  k_commit_period<<<n_blocks(m), kBlock, 0, stream>>>(
-      period_slab.data_ptr<float>(), slots.data_ptr<int32_t>(), m,
-      (float)cur_period);
-}
-
-void apply_adam(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
-                torch::Tensor slots, torch::Tensor grad, double lr_t,
-                double beta1, double beta2, double epsilon) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_adam<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), mom.data_ptr<float>(), vel.data_ptr<float>(),
-      slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr_t,
-      (float)beta1, (float)beta2, (float)epsilon);
-}
-
-void apply_adam_dev(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
-                    torch::Tensor slots, torch::Tensor grad, double lr,
-                    double beta1, double beta2, double epsilon,
-                    torch::Tensor powers) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_adam_dev<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), mom.data_ptr<float>(), vel.data_ptr<float>(),
-      slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr,
-      (float)beta1, (float)beta2, (float)epsilon,
-      powers.data_ptr<float>());
-}
-
-void update_powers(torch::Tensor powers, double beta1, double beta2) {
-  auto stream = current_hip_stream();
-  k_update_powers<<<1, 64, 0, stream>>>(powers.data_ptr<float>(),
-                                        (float)beta1, (float)beta2);
-}
-
-void apply_adamw(torch::Tensor w, torch::Tensor mom, torch::Tensor vel,
-                 torch::Tensor slots, torch::Tensor grad, double lr_t,
-                 double lr, double beta1, double beta2, double epsilon,
-                 double weight_decay) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_adamw<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), mom.data_ptr<float>(), vel.data_ptr<float>(),
-      slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr_t,
-      (float)lr, (float)beta1, (float)beta2, (float)epsilon,
-      (float)weight_decay);
-}
-
-void apply_rmsprop(torch::Tensor w, torch::Tensor vel, torch::Tensor slots,
-                   torch::Tensor grad, double lr, double beta2,
-                   double epsilon) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_rmsprop<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), vel.data_ptr<float>(), slots.data_ptr<int32_t>(),
-      grad.data_ptr<float>(), m, dim, (float)lr, (float)beta2,
-      (float)epsilon);
-}
-
-void apply_ftrl(torch::Tensor w, torch::Tensor n, torch::Tensor z,
-                torch::Tensor slots, torch::Tensor grad, double lr, double l1,
-                double l2, double lr_power, double l2_shrinkage) {
-  int m = slots.numel();
-  if (m == 0) return;
-  int dim = w.size(1);
-  auto stream = current_hip_stream();
-  k_apply_ftrl<<<n_blocks((int64_t)m * dim), kBlock, 0, stream>>>(
-      w.data_ptr<float>(), n.data_ptr<float>(), z.data_ptr<float>(),
-      slots.data_ptr<int32_t>(), grad.data_ptr<float>(), m, dim, (float)lr,
-      (float)l1, (float)l2, (float)lr_power, (float)l2_shrinkage);
-}
-
 void register_dense(pybind11::module_& mod);      // dense_kernels.hip
 void register_gru(pybind11::module_& mod);        // gru_kernels.hip
 void register_attention(pybind11::module_& mod);  // attention_kernels.hip
 void register_fp8(pybind11::module_& mod);        // fp8_kernels.hip
 void register_ev_read(pybind11::module_& mod);    // ev_read_kernels.hip
+void register_ev_apply(pybind11::module_& mod);   // ev_apply_kernels.hip
 void register_loss(pybind11::module_& mod);       // loss_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
@@ -1892,6 +1606,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_attention(mod);
   register_fp8(mod);
   register_ev_read(mod);
+  register_ev_apply(mod);
   register_loss(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
@@ -1924,15 +1639,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   mod.def("pooled_bwd", &pooled_bwd);
   mod.def("group_pooled_bwd_seg", &group_pooled_bwd_seg);
   mod.attr("BWD_SEG_R") = (int64_t)kSegR;
-  mod.def("apply_sgd", &apply_sgd);
-  mod.def("apply_adagrad", &apply_adagrad);
-  mod.def("apply_adagrad_decay", &apply_adagrad_decay);
-  mod.def("apply_adam", &apply_adam);
-  mod.def("apply_adamw", &apply_adamw);
-  mod.def("apply_adam_dev", &apply_adam_dev);
-  mod.def("update_powers", &update_powers);
-  mod.def("apply_rmsprop", &apply_rmsprop);
-  mod.def("apply_ftrl", &apply_ftrl);
   mod.attr("EMPTY_KEY") = EMPTY_KEY;
   mod.attr("PAD_KEY") = INT64_MAX;
 }

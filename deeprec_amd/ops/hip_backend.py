@@ -20,7 +20,8 @@ from deeprec_amd.embedding.options import (
     L2WeightEvict,
 )
 from deeprec_amd.ops.build_ext import require_extension
-from deeprec_amd.ops.common import COMBINER_ID, KEY_BITS, DedupResult
+from deeprec_amd.ops.common import (
+    COMBINER_ID, KEY_BITS, DedupResult, bias_corrected_lr, optimizer_slabs)
 
 _LOAD_FACTOR = 0.6
 
@@ -647,72 +648,59 @@ class HbmStorage:
 
 # ---------------- optimizer dispatch ----------------
 
+def _adam_args(h, b1p, b2p):
+    return (bias_corrected_lr(h["lr"], b1p, b2p), h["beta1"], h["beta2"],
+            h["epsilon"])
+
+
+# rule -> (entry point, its scalar arguments from the hyper dict). Every
+# entry point is called as f(values, *slabs, slots, grad, *scalars), the
+# slabs being the rule's OPTIMIZER_SLABS.
+_APPLY_RULES = {
+    "sgd": ("apply_sgd", lambda h: (h["lr"],)),
+    "adagrad": ("apply_adagrad",
+                lambda h: (h["lr"], h.get("epsilon", 0.0))),
+    "adagrad_decay": ("apply_adagrad_decay", lambda h: (
+        h["lr"], h.get("epsilon", 0.0),
+        float(h["global_step"] // max(1, h["accumulator_decay_step"])),
+        h["accumulator_decay_rate"], h["accumulator_baseline"])),
+    "adam": ("apply_adam", lambda h: _adam_args(
+        h, h["beta1"] ** h["step_t"], h["beta2"] ** h["step_t"])),
+    "adamw": ("apply_adamw", lambda h: (
+        bias_corrected_lr(h["lr"], h["beta1"] ** h["step_t"],
+                          h["beta2"] ** h["step_t"]),
+        h["lr"], h["beta1"], h["beta2"], h["epsilon"], h["weight_decay"])),
+    "adam_async": ("apply_adam", lambda h: _adam_args(
+        h, h["beta1_power"], h["beta2_power"])),
+    "adam_dev": ("apply_adam_dev", lambda h: (
+        h["lr"], h["beta1"], h["beta2"], h["epsilon"], h["powers_dev"])),
+    "rmsprop": ("apply_rmsprop",
+                lambda h: (h["lr"], h["beta2"], h["epsilon"])),
+    "ftrl": ("apply_ftrl", lambda h: (
+        h["lr"], h["l1"], h["l2"], h["lr_power"],
+        h.get("l2_shrinkage", 0.0))),
+}
+
+
 def sparse_apply(name: str, storage: HbmStorage, slots, grad, hyper: dict):
     if getattr(storage, "inference_only", False):
         raise RuntimeError(
             f"{type(storage).__name__} is inference-only: its rows are "
             "quantized and cannot take a sparse optimizer apply")
-    ext = storage.ext
     grad = grad.float().contiguous()
     slots = slots.to(torch.int32)
-    w = storage.values
-    d = storage.dim
-    if name == "sgd":
-        ext.apply_sgd(w, slots, grad, hyper["lr"])
-    elif name == "adagrad":
-        accum = storage.get_slab("adagrad_accum", d,
-                                 hyper.get("initial_accumulator", 0.1))
-        ext.apply_adagrad(w, accum, slots, grad, hyper["lr"],
-                          hyper.get("epsilon", 0.0))
-    elif name == "adagrad_decay":
-        accum = storage.get_slab("adagrad_accum", d,
-                                 hyper.get("initial_accumulator", 0.1))
-        period = storage.get_slab("adagrad_decay_period", 1, 0.0)
-        cur_period = float(hyper["global_step"]
-                           // max(1, hyper["accumulator_decay_step"]))
-        ext.apply_adagrad_decay(
-            w, accum, period, slots, grad, hyper["lr"],
-            hyper.get("epsilon", 0.0), cur_period,
-            hyper["accumulator_decay_rate"], hyper["accumulator_baseline"])
-    elif name in ("adam", "adamw"):
-        import math as _m
-        mom = storage.get_slab("adam_m", d, 0.0)
-        vel = storage.get_slab("adam_v", d, 0.0)
-        b1, b2 = hyper["beta1"], hyper["beta2"]
-        t = hyper["step_t"]
-        lr_t = hyper["lr"] * _m.sqrt(1 - b2 ** t) / (1 - b1 ** t)
-        if name == "adam":
-            ext.apply_adam(w, mom, vel, slots, grad, lr_t, b1, b2,
-                           hyper["epsilon"])
-        else:
-            ext.apply_adamw(w, mom, vel, slots, grad, lr_t, hyper["lr"],
-                            b1, b2, hyper["epsilon"], hyper["weight_decay"])
-    elif name == "adam_async":
-        import math as _m
-        b1, b2 = hyper["beta1"], hyper["beta2"]
+    rule = name
+    if name == "adam_async":  # device powers are tested first
         if hyper.get("powers_dev") is not None:
-            mom = storage.get_slab("adam_m", d, 0.0)
-            vel = storage.get_slab("adam_v", d, 0.0)
-            ext.apply_adam_dev(w, mom, vel, slots, grad, hyper["lr"],
-                               b1, b2, hyper["epsilon"],
-                               hyper["powers_dev"])
+            rule = "adam_dev"
         elif hyper.get("sparse_rmsprop"):
-            vel = storage.get_slab("adam_v", d, 0.0)
-            ext.apply_rmsprop(w, vel, slots, grad, hyper["lr"], b2,
-                              hyper["epsilon"])
-        else:
-            mom = storage.get_slab("adam_m", d, 0.0)
-            vel = storage.get_slab("adam_v", d, 0.0)
-            lr_t = hyper["lr"] * _m.sqrt(1 - hyper["beta2_power"]) / \
-                (1 - hyper["beta1_power"])
-            ext.apply_adam(w, mom, vel, slots, grad, lr_t, b1, b2,
-                           hyper["epsilon"])
-    elif name == "ftrl":
-        n = storage.get_slab("ftrl_accum", d, 0.1)
-        z = storage.get_slab("ftrl_linear", d, 0.0)
-        ext.apply_ftrl(w, n, z, slots, grad, hyper["lr"], hyper["l1"],
-                       hyper["l2"], hyper["lr_power"],
-                       hyper.get("l2_shrinkage", 0.0))
-    else:
+            rule = "rmsprop"
+    elif name in ("adam_dev", "rmsprop"):
+        rule = None  # forms of adam_async, not optimizer names
+    if rule not in _APPLY_RULES:
         raise ValueError(f"unknown sparse optimizer {name!r}")
+    entry, scalars = _APPLY_RULES[rule]
+    getattr(storage.ext, entry)(
+        storage.values, *optimizer_slabs(storage, rule, hyper), slots, grad,
+        *scalars(hyper))
 

@@ -1,8 +1,8 @@
 """CPU / fp32-reference sparse optimizer applies on EV slots.
 
-These are the semantics the fused HIP kernels
-(ops/hip/ev_kernels.hip: sparse_apply_* ) must reproduce; GPU numerics
-tests compare against this module.
+These are the semantics the fused HIP applies (ops/hip/ev_apply_kernels.hip:
+k_sparse_apply<Rule>, one rule struct per function here) must reproduce;
+GPU numerics tests compare against this module.
 
 Reference kernels: kernels/training_ali_ops.cc (CPU) and
 training_ali_ops_gpu.cu.cc (kv_sparse_apply_{adagrad,ftrl,adam_async}).
@@ -11,14 +11,34 @@ skip un-admitted keys (slot < 0).
 """
 from __future__ import annotations
 
-import math
-
 import torch
+
+from deeprec_amd.ops.common import bias_corrected_lr, optimizer_slabs
 
 
 def _adm(storage, slots, grad):
     mask = slots >= 0
     return slots[mask].long(), grad[mask].float()
+
+
+def _second_moment(v, s, g, beta2):
+    vn = beta2 * v[s] + (1 - beta2) * g * g
+    v[s] = vn
+    return vn
+
+
+def _adam_step(storage, rule, s, g, lr_t, beta1, beta2, epsilon):
+    """Updates both moments; returns what the values move by."""
+    m, v = optimizer_slabs(storage, rule, {})
+    mn = beta1 * m[s] + (1 - beta1) * g
+    vn = _second_moment(v, s, g, beta2)
+    m[s] = mn
+    return lr_t * mn / (vn.sqrt() + epsilon)
+
+
+def _adagrad_step(storage, s, g, a, lr, epsilon):
+    """a: the accumulator after this gradient."""
+    storage.values[s] -= lr * g / (a.sqrt() + epsilon)
 
 
 def apply_sgd(storage, slots, grad, lr, **_):
@@ -29,10 +49,11 @@ def apply_sgd(storage, slots, grad, lr, **_):
 def apply_adagrad(storage, slots, grad, lr, initial_accumulator=0.1,
                   epsilon=0.0, **_):
     s, g = _adm(storage, slots, grad)
-    accum = storage.get_slab("adagrad_accum", storage.dim, initial_accumulator)
+    accum, = optimizer_slabs(
+        storage, "adagrad", dict(initial_accumulator=initial_accumulator))
     a = accum[s] + g * g
     accum[s] = a
-    storage.values[s] -= lr * g / (a.sqrt() + epsilon)
+    _adagrad_step(storage, s, g, a, lr, epsilon)
 
 
 def apply_adagrad_decay(storage, slots, grad, lr, global_step,
@@ -46,28 +67,25 @@ def apply_adagrad_decay(storage, slots, grad, lr, global_step,
     at accumulator_baseline. Per-key decay bookkeeping lives in a 1-wide
     slab so sparsely-touched keys decay by the right number of periods."""
     s, g = _adm(storage, slots, grad)
-    accum = storage.get_slab("adagrad_accum", storage.dim, initial_accumulator)
-    period_slab = storage.get_slab("adagrad_decay_period", 1, 0.0)
+    accum, period_slab = optimizer_slabs(
+        storage, "adagrad_decay",
+        dict(initial_accumulator=initial_accumulator))
     cur_period = float(global_step // max(1, accumulator_decay_step))
     dp = (cur_period - period_slab[s, 0]).clamp(min=0)
     decay = torch.pow(torch.tensor(accumulator_decay_rate), dp).unsqueeze(1)
     a = (accum[s] * decay).clamp(min=accumulator_baseline) + g * g
     accum[s] = a
     period_slab[s, 0] = cur_period
-    storage.values[s] -= lr * g / (a.sqrt() + epsilon)
+    _adagrad_step(storage, s, g, a, lr, epsilon)
 
 
 def apply_adam(storage, slots, grad, lr, step_t, beta1=0.9, beta2=0.999,
                epsilon=1e-8, **_):
     """step_t: 1-based global apply count for bias correction."""
     s, g = _adm(storage, slots, grad)
-    m = storage.get_slab("adam_m", storage.dim, 0.0)
-    v = storage.get_slab("adam_v", storage.dim, 0.0)
-    mn = beta1 * m[s] + (1 - beta1) * g
-    vn = beta2 * v[s] + (1 - beta2) * g * g
-    m[s], v[s] = mn, vn
-    lr_t = lr * math.sqrt(1 - beta2 ** step_t) / (1 - beta1 ** step_t)
-    storage.values[s] -= lr_t * mn / (vn.sqrt() + epsilon)
+    lr_t = bias_corrected_lr(lr, beta1 ** step_t, beta2 ** step_t)
+    storage.values[s] -= _adam_step(storage, "adam", s, g, lr_t, beta1,
+                                    beta2, epsilon)
 
 
 def apply_adam_async(storage, slots, grad, lr, beta1_power, beta2_power,
@@ -79,31 +97,23 @@ def apply_adam_async(storage, slots, grad, lr, beta1_power, beta2_power,
     are per-variable scalars maintained by the caller. With sparse_rmsprop
     the m accumulator is skipped and v behaves like RMSProp."""
     s, g = _adm(storage, slots, grad)
-    v = storage.get_slab("adam_v", storage.dim, 0.0)
     if sparse_rmsprop:
-        vn = beta2 * v[s] + (1 - beta2) * g * g
-        v[s] = vn
+        v, = optimizer_slabs(storage, "rmsprop", {})
+        vn = _second_moment(v, s, g, beta2)
         storage.values[s] -= lr * g / (vn.sqrt() + epsilon)
         return
-    m = storage.get_slab("adam_m", storage.dim, 0.0)
-    mn = beta1 * m[s] + (1 - beta1) * g
-    vn = beta2 * v[s] + (1 - beta2) * g * g
-    m[s], v[s] = mn, vn
-    lr_t = lr * math.sqrt(1 - beta2_power) / (1 - beta1_power)
-    storage.values[s] -= lr_t * mn / (vn.sqrt() + epsilon)
+    lr_t = bias_corrected_lr(lr, beta1_power, beta2_power)
+    storage.values[s] -= _adam_step(storage, "adam_async", s, g, lr_t,
+                                    beta1, beta2, epsilon)
 
 
 def apply_adamw(storage, slots, grad, lr, step_t, weight_decay=0.01,
                 beta1=0.9, beta2=0.999, epsilon=1e-8, **_):
     s, g = _adm(storage, slots, grad)
-    m = storage.get_slab("adam_m", storage.dim, 0.0)
-    v = storage.get_slab("adam_v", storage.dim, 0.0)
-    mn = beta1 * m[s] + (1 - beta1) * g
-    vn = beta2 * v[s] + (1 - beta2) * g * g
-    m[s], v[s] = mn, vn
-    lr_t = lr * math.sqrt(1 - beta2 ** step_t) / (1 - beta1 ** step_t)
+    lr_t = bias_corrected_lr(lr, beta1 ** step_t, beta2 ** step_t)
+    step = _adam_step(storage, "adamw", s, g, lr_t, beta1, beta2, epsilon)
     w = storage.values[s]
-    storage.values[s] = w - lr_t * mn / (vn.sqrt() + epsilon) - lr * weight_decay * w
+    storage.values[s] = w - step - lr * weight_decay * w
 
 
 def apply_ftrl(storage, slots, grad, lr, l1=0.0, l2=0.0,
@@ -111,8 +121,7 @@ def apply_ftrl(storage, slots, grad, lr, l1=0.0, l2=0.0,
     """FTRL-proximal (reference: KvSparseApplyFtrlOp,
     training_ali_ops.cc:431); l2_shrinkage != 0 is the FtrlV2 variant."""
     s, g = _adm(storage, slots, grad)
-    n = storage.get_slab("ftrl_accum", storage.dim, 0.1)
-    z = storage.get_slab("ftrl_linear", storage.dim, 0.0)
+    n, z = optimizer_slabs(storage, "ftrl", {})
     w = storage.values[s].float()
     n_old = n[s]
     n_new = n_old + g * g

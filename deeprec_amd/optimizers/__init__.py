@@ -8,7 +8,7 @@ every stock optimizer gained, e.g. python/training/adagrad.py:141-154).
 
 Dense updates delegate to torch.optim (hipBLASLt-backed fused kernels);
 sparse EV updates go through the fused HIP applies
-(ops/hip/ev_kernels.hip) on GPU or ops/sparse_optim_cpu.py on CPU.
+(ops/hip/ev_apply_kernels.hip) on GPU or ops/sparse_optim_cpu.py on CPU.
 """
 from __future__ import annotations
 
