@@ -12,6 +12,7 @@ Distributed (one process per GPU):
 from __future__ import annotations
 
 import argparse
+import inspect
 import logging
 import os
 import time
@@ -99,6 +100,13 @@ def build_argparser():
                         "train.py uses tf.clip_by_norm(grad, 5))")
     p.add_argument("--lr_decay", default=None, metavar="STEPS:RATE",
                    help="exponential learning-rate decay, e.g. 1000:0.9")
+    p.add_argument("--gru_hidden", type=int, default=None,
+                   help="DIEN recurrent state width (default: the model's "
+                        "own; the reference DIEN runs 36)")
+    p.add_argument("--item_dim", type=int, default=None,
+                   help="item embedding width of the sequence models "
+                        "(default: the model's own; the reference DIEN "
+                        "runs 36)")
     p.add_argument("--eval_steps", type=int, default=0,
                    help="after training, evaluate N batches (no inserts, "
                         "no training) and print loss/accuracy/AUC — the "
@@ -130,6 +138,22 @@ def make_ev_option(args) -> EmbeddingVariableOption:
     elif args.ev_elimination == "l2":
         opt.evict_option = L2WeightEvict(l2_weight_threshold=0.01)
     return opt
+
+
+def width_kwargs(args) -> dict:
+    """--gru_hidden / --item_dim as constructor keywords: only those given,
+    and only for a model whose constructor names them."""
+    params = inspect.signature(MODEL_REGISTRY[args.model]).parameters
+    kw = {}
+    for name in ("gru_hidden", "item_dim"):
+        value = getattr(args, name)
+        if value is None:
+            continue
+        if name not in params:
+            raise SystemExit(f"--{name} does not apply to --model "
+                             f"{args.model}")
+        kw[name] = value
+    return kw
 
 
 def _parquet_batches(path, batch_size, device, num_sparse,
@@ -175,6 +199,7 @@ def main(argv=None):
                     ev_option=make_ev_option(args))
     if args.sharded and world > 1:
         model_kw["sharded"] = True
+    model_kw.update(width_kwargs(args))
     model = MODEL_REGISTRY[args.model](**model_kw)
 
     from deeprec_amd.optimizers import make_optimizer

@@ -3,7 +3,8 @@
 See ops/hip/gru_kernels.hip. torch-GRU-compatible weights (weight_ih
 [3H,D] rows [r;z;n], weight_hh [3H,H], bias_ih, bias_hh). The x-side
 projection for all timesteps is one MFMA GEMM; the recurrence is one
-kernel; all weight/input grads are three GEMM calls over the stored
+kernel (one wave per sample for H <= 32, 16-sample MFMA tiles for
+32 < H <= 64); all weight/input grads are three GEMM calls over the stored
 per-gate pre-activation grads. AUGRU takes a per-(sample, step) attention
 factor a: h' = (1-a) h + a * GRU(h, x) and returns its gradient.
 CPU path: reference loop with identical math (the numerics oracle).
@@ -19,7 +20,7 @@ import torch.nn as nn
 
 class _FusedGRUFunction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x, w_ih, b_ih, w_hh, b_hh, alpha):
+    def forward(ctx, x, w_ih, b_ih, w_hh, b_hh, alpha, tile=False):
         from deeprec_amd.ops.build_ext import require_extension
         ext = require_extension()
         B, T, D = x.shape
@@ -31,8 +32,10 @@ class _FusedGRUFunction(torch.autograd.Function):
         bh = b_hh.detach().float()
         a = alpha.float().contiguous() if alpha is not None \
             else torch.Tensor()
-        h_out, gates = ext.gru_fwd(x3.view(B, T, 3 * H), u16, bh, a, B, T, H)
+        fwd = ext.gru_tile_fwd if tile else ext.gru_fwd
+        h_out, gates = fwd(x3.view(B, T, 3 * H), u16, bh, a, B, T, H)
         ctx.ext = ext
+        ctx.tile = tile
         ctx.dims = (B, T, D, H)
         ctx.x_dtype = x.dtype
         ctx.has_alpha = alpha is not None
@@ -45,7 +48,8 @@ class _FusedGRUFunction(torch.autograd.Function):
         ext = ctx.ext
         B, T, D, H = ctx.dims
         x16, w_ih16, u16, bh, h_out, gates, a = ctx.saved_tensors
-        dpre_x, dpre_h, dalpha = ext.gru_bwd(
+        bwd = ext.gru_tile_bwd if ctx.tile else ext.gru_bwd
+        dpre_x, dpre_h, dalpha = bwd(
             dh_out.float(), h_out, gates, u16, bh,
             a if ctx.has_alpha else torch.Tensor(), B, T, H)
         dpx = dpre_x.view(B * T, 3 * H)
@@ -56,7 +60,7 @@ class _FusedGRUFunction(torch.autograd.Function):
             dim=1).reshape(B * T, H).to(torch.bfloat16).contiguous()
         dw_hh, db_hh = ext.linear_dw(dpre_h.view(B * T, 3 * H), h_prev, True)
         return dx, dw_ih, db_ih, dw_hh, db_hh, \
-            (dalpha if ctx.has_alpha else None)
+            (dalpha if ctx.has_alpha else None), None
 
 
 def _cpu_gru(x, w_ih, b_ih, w_hh, b_hh, alpha):
@@ -83,13 +87,31 @@ def _cpu_gru(x, w_ih, b_ih, w_hh, b_hh, alpha):
     return torch.stack(outs, dim=1)
 
 
+WAVE_MAX_HIDDEN = 32    # gru_fwd / gru_bwd: one wave per sample
+MAX_HIDDEN = 64         # gru_tile_fwd / gru_tile_bwd: 16 samples per wave
+
+
 class FusedGRU(nn.Module):
     """batch_first GRU (optionally attention-gated) with torch-compatible
-    parameters. forward(x [B,T,D], alpha=None) -> h_seq [B,T,H]."""
+    parameters. forward(x [B,T,D], alpha=None) -> h_seq [B,T,H].
 
-    def __init__(self, input_size: int, hidden_size: int):
+    impl picks the recurrence kernels on the GPU: "auto" (what every model
+    uses) runs the wave kernels for H <= 32 and the tile-MFMA kernels for
+    32 < H <= 64; "tile" forces the tile kernels at any H <= 64; "wave"
+    forces the wave kernels and raises for H > 32."""
+
+    def __init__(self, input_size: int, hidden_size: int,
+                 impl: str = "auto"):
         super().__init__()
-        assert hidden_size <= 32, "fused GRU supports hidden size <= 32"
+        assert hidden_size <= MAX_HIDDEN, \
+            f"fused GRU supports hidden size <= {MAX_HIDDEN}"
+        assert impl in ("auto", "wave", "tile"), impl
+        if impl == "wave" and hidden_size > WAVE_MAX_HIDDEN:
+            raise ValueError(
+                f"impl='wave' supports hidden size <= {WAVE_MAX_HIDDEN}")
+        # auto: the wave kernels up to their limit, the tile kernels above
+        self.tile = impl == "tile" or (impl == "auto"
+                                       and hidden_size > WAVE_MAX_HIDDEN)
         self.input_size = input_size
         self.hidden_size = hidden_size
         H = hidden_size
@@ -106,6 +128,6 @@ class FusedGRU(nn.Module):
         if x.device.type == "cuda":
             return _FusedGRUFunction.apply(
                 x, self.weight_ih_l0, self.bias_ih_l0, self.weight_hh_l0,
-                self.bias_hh_l0, alpha)
+                self.bias_hh_l0, alpha, self.tile)
         return _cpu_gru(x, self.weight_ih_l0, self.bias_ih_l0,
                         self.weight_hh_l0, self.bias_hh_l0, alpha)
