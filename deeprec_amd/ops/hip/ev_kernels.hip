@@ -1599,6 +1599,7 @@ void register_fp8(pybind11::module_& mod);        // fp8_kernels.hip
 void register_ev_read(pybind11::module_& mod);    // ev_read_kernels.hip
 void register_ev_apply(pybind11::module_& mod);   // ev_apply_kernels.hip
 void register_loss(pybind11::module_& mod);       // loss_kernels.hip
+void register_cross(pybind11::module_& mod);      // cross_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_dense(mod);
@@ -1608,6 +1609,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_ev_read(mod);
   register_ev_apply(mod);
   register_loss(mod);
+  register_cross(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);
