@@ -107,6 +107,9 @@ def build_argparser():
                    help="item embedding width of the sequence models "
                         "(default: the model's own; the reference DIEN "
                         "runs 36)")
+    p.add_argument("--fused_experts", action="store_true",
+                   help="mmoe / ple: run the expert block and the gate "
+                        "mixture on the grouped-expert kernels")
     p.add_argument("--eval_steps", type=int, default=0,
                    help="after training, evaluate N batches (no inserts, "
                         "no training) and print loss/accuracy/AUC — the "
@@ -141,8 +144,8 @@ def make_ev_option(args) -> EmbeddingVariableOption:
 
 
 def width_kwargs(args) -> dict:
-    """--gru_hidden / --item_dim as constructor keywords: only those given,
-    and only for a model whose constructor names them."""
+    """--gru_hidden / --item_dim / --fused_experts as constructor keywords:
+    only those given, and only for a model whose constructor names them."""
     params = inspect.signature(MODEL_REGISTRY[args.model]).parameters
     kw = {}
     for name in ("gru_hidden", "item_dim"):
@@ -153,6 +156,11 @@ def width_kwargs(args) -> dict:
             raise SystemExit(f"--{name} does not apply to --model "
                              f"{args.model}")
         kw[name] = value
+    if args.fused_experts:
+        if "fused_experts" not in params:
+            raise SystemExit("--fused_experts does not apply to --model "
+                             f"{args.model}")
+        kw["fused_experts"] = True
     return kw
 
 

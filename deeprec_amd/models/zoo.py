@@ -231,13 +231,21 @@ class DSSM(RecModelBase):
 
 
 class MMoE(RecModelBase):
-    """Multi-gate mixture of experts, 2 tasks (reference: modelzoo/mmoe)."""
+    """Multi-gate mixture of experts, 2 tasks (reference: modelzoo/mmoe).
+
+    fused_experts=True runs the expert block and the gate mixture as one
+    autograd node on the grouped-expert kernels (ops/fused_moe.py) where
+    they apply — the GPU, bf16, batch % 16 == 0, at most 16 experts and 4
+    tasks; anything else takes the per-expert path. Parameters and
+    state_dict keys are the same either way."""
 
     def __init__(self, embedding_dim=16, n_experts=8, expert_sizes=(256, 128),
-                 tower_sizes=(64,), n_tasks=2, device="cpu", bf16=True, **kw):
+                 tower_sizes=(64,), n_tasks=2, device="cpu", bf16=True,
+                 fused_experts=False, **kw):
         super().__init__(embedding_dim, device, bf16, name="mmoe", **kw)
         in_dim = NUM_DENSE + self.num_sparse * embedding_dim
         self.n_tasks = n_tasks
+        self.fused_experts = fused_experts
         self.experts = nn.ModuleList(
             [make_mlp(expert_sizes, in_dim, device, self.bf16)
              for _ in range(n_experts)])
@@ -252,6 +260,13 @@ class MMoE(RecModelBase):
     def forward(self, dense, sparse_ids, train=True):
         emb = self.sparse_feats(sparse_ids, train)
         x = torch.cat([dense.to(emb.dtype), emb.flatten(1)], 1)
+        if self.fused_experts:
+            from deeprec_amd.ops.fused_moe import expert_mixture
+            gl = torch.stack([g(x.float()) for g in self.gates], 1)  # [B,T,E]
+            with self.amp():
+                return [self.towers[t](mix.to(self.compute_dtype)).float()
+                        .squeeze(1) for t, mix in enumerate(
+                            expert_mixture(x, list(self.experts), gl))]
         with self.amp():
             ex = torch.stack([e(x) for e in self.experts], 1)  # [B,E,H]
         ex = ex.float()
@@ -362,13 +377,25 @@ class DBMTL(RecModelBase):
 
 class PLE(RecModelBase):
     """Progressive layered extraction (CGC single level, 2 tasks)
-    (reference: modelzoo/ple)."""
+    (reference: modelzoo/ple).
+
+    fused_experts=True: as in MMoE, with the shared and the task-specific
+    experts as one group and a [task, expert] mask that keeps each task to
+    the shared experts and its own."""
 
     def __init__(self, embedding_dim=16, expert_sizes=(256, 128),
                  tower_sizes=(64,), n_shared=2, n_spec=2, device="cpu",
-                 bf16=True, **kw):
+                 bf16=True, fused_experts=False, **kw):
         super().__init__(embedding_dim, device, bf16, name="ple", **kw)
         in_dim = NUM_DENSE + self.num_sparse * embedding_dim
+        self.fused_experts = fused_experts
+        # experts in the order [shared | task 0's | task 1's]
+        self.expert_mask = torch.zeros(2, n_shared + 2 * n_spec,
+                                       dtype=torch.uint8)
+        self.expert_mask[:, :n_shared] = 1
+        for t in range(2):
+            lo = n_shared + t * n_spec
+            self.expert_mask[t, lo:lo + n_spec] = 1
         mk = lambda: make_mlp(expert_sizes, in_dim, device, self.bf16)
         self.shared = nn.ModuleList([mk() for _ in range(n_shared)])
         self.spec = nn.ModuleList(
@@ -383,6 +410,8 @@ class PLE(RecModelBase):
     def forward(self, dense, sparse_ids, train=True):
         emb = self.sparse_feats(sparse_ids, train)
         x = torch.cat([dense.to(emb.dtype), emb.flatten(1)], 1)
+        if self.fused_experts:
+            return self._forward_fused(x)
         with self.amp():
             shared = [e(x) for e in self.shared]
             outs = []
@@ -394,6 +423,25 @@ class PLE(RecModelBase):
                 outs.append(self.towers[t](
                     mix.to(self.compute_dtype)).float().squeeze(1))
         return outs
+
+    def _forward_fused(self, x):
+        from deeprec_amd.ops.fused_moe import expert_mixture
+        experts = list(self.shared) + [e for sp in self.spec for e in sp]
+        n_sh, n_sp = len(self.shared), len(self.spec[0])
+        with self.amp():
+            # each gate's logits [shared | own], spread over the group's
+            # order; the masked slots are never read
+            rows = []
+            for t in range(2):
+                g = self.gates[t](x.float())
+                pad = g.new_zeros(g.shape[0], n_sp)
+                own = [pad] * 2
+                own[t] = g[:, n_sh:]
+                rows.append(torch.cat([g[:, :n_sh]] + own, 1))
+            mixes = expert_mixture(x, experts, torch.stack(rows, 1),
+                                   self.expert_mask)
+            return [self.towers[t](mix.to(self.compute_dtype)).float()
+                    .squeeze(1) for t, mix in enumerate(mixes)]
 
     loss_fn = MMoE.loss_fn
 

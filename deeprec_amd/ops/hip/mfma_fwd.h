@@ -1,7 +1,8 @@
 // mfma_fwd.h — the forward GEMM's operand side, shared by the kernels that
 // compute A[M,K] @ W[N,K]^T on v_mfma_f32_16x16x32_bf16 and differ only in
 // their epilogue (dense_kernels.hip: activation; cross_kernels.hip: the
-// DCNv2 cross update). Fragment layouts per the CDNA4 ISA: A: row=lane%16,
+// DCNv2 cross update; moe_kernels.hip: grouped experts and the gate
+// mixture). Fragment layouts per the CDNA4 ISA: A: row=lane%16,
 // k=8*(lane/16)+i; B: col=lane%16, same k; D: col=lane%16,
 // row=4*(lane/16)+i.
 #pragma once

@@ -3,11 +3,13 @@ harness analog). Runs each model for a fixed step count on the current
 device and writes a markdown table.
 
 Usage: python tools/benchmark_models.py [--steps 30] [--out profiles/...]
-       [--static-seq] [--no-graph]
+       [--static-seq] [--no-graph] [--fused-experts]
 --static-seq builds din/dien/bst with static_seq=True (one padded lookup
 for sequence and target); din and bst then train as a captured hipGraph
 like the dense-feature models. dien stays eager: its auxiliary loss draws a
 permutation and branches on the host.
+--fused-experts builds mmoe and ple with fused_experts=True (grouped-expert
+kernels, ops/fused_moe.py); their rows are then named mmoe+fused, ple+fused.
 Batch sizes follow the reference GPU benchmark config
 (modelzoo/benchmark/gpu/config.yaml: dlrm 8192, wide_and_deep 32768,
 deepfm 8192, dien 16384).
@@ -39,8 +41,11 @@ DEFAULT_BATCH = 8192
 CAPTURABLE_SEQ = {"din", "bst"}
 
 
+FUSED_EXPERT_MODELS = {"mmoe", "ple"}
+
+
 def bench_model(name, steps, warmup, device, use_graph=True,
-                static_seq=False):
+                static_seq=False, fused_experts=False):
     from deeprec_amd.data.synthetic import CriteoSyntheticDataset
     from deeprec_amd.embedding.options import EmbeddingVariableOption
     from deeprec_amd.models import MODEL_REGISTRY, SEQUENCE_MODELS
@@ -54,6 +59,8 @@ def bench_model(name, steps, warmup, device, use_graph=True,
     kw = {}
     if is_seq and static_seq:
         kw["static_seq"] = True
+    if fused_experts and name in FUSED_EXPERT_MODELS:
+        kw["fused_experts"] = True
     if use_graph:
         kw["ev_option"] = EmbeddingVariableOption(init_capacity=1 << 23)
     m = MODEL_REGISTRY[name](device=device, bf16=device.type == "cuda",
@@ -134,6 +141,9 @@ def main():
     p.add_argument("--static-seq", action="store_true",
                    help="sequence models use the static-shape padded "
                         "lookup; din and bst are captured")
+    p.add_argument("--fused-experts", action="store_true",
+                   help="mmoe and ple run their experts and gate mixture "
+                        "on the grouped-expert kernels")
     p.add_argument("--no-graph", action="store_true",
                    help="step eagerly even where capture is possible")
     args = p.parse_args()
@@ -148,7 +158,10 @@ def main():
             batch, sps, ms = bench_model(name, args.steps, args.warmup,
                                          device,
                                          use_graph=not args.no_graph,
-                                         static_seq=args.static_seq)
+                                         static_seq=args.static_seq,
+                                         fused_experts=args.fused_experts)
+            if args.fused_experts and name in FUSED_EXPERT_MODELS:
+                name += "+fused"
             rows.append((name, batch, sps, ms))
             print(f"{name:18s} batch={batch:6d}  {sps:12.0f} samples/s  "
                   f"{ms:8.3f} ms/step", flush=True)
