@@ -1,3 +1,5 @@
+import functools
+
 from deeprec_amd.models.dlrm import DLRM  # noqa: F401
 from deeprec_amd.models.zoo import (  # noqa: F401
     DBMTL, DCN, DSSM, ESMM, WDL, DeepFM, MMoE, MaskNet,
@@ -7,7 +9,9 @@ from deeprec_amd.models.sequence import BST, DIEN, DIN  # noqa: F401
 
 MODEL_REGISTRY = {
     "dlrm": DLRM, "wdl": WDL, "wide_and_deep": WDL, "deepfm": DeepFM,
-    "dcn": DCN, "dcnv2": lambda **kw: DCN(v2=True, **kw), "dssm": DSSM,
+    "dcn": DCN, "dssm": DSSM,
+    # a partial, not a lambda: the runner reads the constructor's keywords
+    "dcnv2": functools.partial(DCN, v2=True),
     "mmoe": MMoE, "esmm": ESMM, "dbmtl": DBMTL, "ple": PLE,
     "masknet": MaskNet, "simple_multitask": SimpleMultiTask,
     "mlperf_dlrm_dcn": MLPerfDLRMDCN,

@@ -110,6 +110,9 @@ def build_argparser():
     p.add_argument("--fused_experts", action="store_true",
                    help="mmoe / ple: run the expert block and the gate "
                         "mixture on the grouped-expert kernels")
+    p.add_argument("--fused_cross_train", action="store_true",
+                   help="dcnv2 / mlperf_dlrm_dcn: train the cross stack as "
+                        "one autograd node on the cross kernels")
     p.add_argument("--eval_steps", type=int, default=0,
                    help="after training, evaluate N batches (no inserts, "
                         "no training) and print loss/accuracy/AUC — the "
@@ -144,8 +147,9 @@ def make_ev_option(args) -> EmbeddingVariableOption:
 
 
 def width_kwargs(args) -> dict:
-    """--gru_hidden / --item_dim / --fused_experts as constructor keywords:
-    only those given, and only for a model whose constructor names them."""
+    """--gru_hidden / --item_dim / --fused_experts / --fused_cross_train as
+    constructor keywords: only those given, and only for a model whose
+    constructor names them."""
     params = inspect.signature(MODEL_REGISTRY[args.model]).parameters
     kw = {}
     for name in ("gru_hidden", "item_dim"):
@@ -156,11 +160,13 @@ def width_kwargs(args) -> dict:
             raise SystemExit(f"--{name} does not apply to --model "
                              f"{args.model}")
         kw[name] = value
-    if args.fused_experts:
-        if "fused_experts" not in params:
-            raise SystemExit("--fused_experts does not apply to --model "
+    for name in ("fused_experts", "fused_cross_train"):
+        if not getattr(args, name):
+            continue
+        if name not in params:
+            raise SystemExit(f"--{name} does not apply to --model "
                              f"{args.model}")
-        kw["fused_experts"] = True
+        kw[name] = True
     return kw
 
 

@@ -91,13 +91,22 @@ class _CrossNet(nn.Module):
     (ops/fused_cross.py) when no gradient is recorded, the input is an
     fp32 GPU matrix and every layer is a plain nn.Linear without hooks;
     anything else (training, CPU, the v1 vector form, low rank, fp8-
-    converted layers) takes the layer-by-layer path. Parameters and
-    state_dict keys are the same either way."""
+    converted layers) takes the layer-by-layer path.
 
-    def __init__(self, dim, n_layers=3, v2=False, low_rank=0, fused=False):
+    fused_train=True runs a v2 stack, full matrix or low rank up to 128,
+    as one autograd node on the cross kernels (ops/fused_cross.py:
+    cross_stack), with or without a gradient, under the same conditions on
+    input and layers; v1, a larger rank, the CPU, fp8-converted layers and
+    hooks take the layer-by-layer path. Eager only: the node has not been
+    run under graph capture. Parameters and state_dict keys are the same
+    whatever the flags."""
+
+    def __init__(self, dim, n_layers=3, v2=False, low_rank=0, fused=False,
+                 fused_train=False):
         super().__init__()
         self.v2 = v2
         self.fused = fused
+        self.fused_train = fused_train
         if v2 and low_rank > 0:
             self.ws = nn.ModuleList([
                 nn.Sequential(nn.Linear(dim, low_rank, bias=False),
@@ -131,7 +140,35 @@ class _CrossNet(nn.Module):
             return None
         return [(w.weight, w.bias) for w in self.ws]
 
+    def _train_layers(self, x0):
+        """The layers as cross_stack takes them, or None where the fused
+        stack does not apply."""
+        from deeprec_amd.ops.fused_cross import MAX_RANK
+        from deeprec_amd.ops.fused_mlp import (_global_module_hooks,
+                                               _has_hooks)
+        if (not self.fused_train or not self.v2 or len(self.ws) == 0
+                or x0.device.type != "cuda" or x0.dtype != torch.float32
+                or x0.dim() != 2 or _global_module_hooks()):
+            return None
+        layers = []
+        for w in self.ws:
+            lins = list(w) if type(w) is nn.Sequential else [w]
+            if (len(lins) > 2 or _has_hooks(w) or lins[-1].bias is None
+                    or any(type(m) is not nn.Linear or _has_hooks(m)
+                           or m.weight.device != x0.device for m in lins)):
+                return None
+            if len(lins) == 2 and (
+                    lins[0].bias is not None
+                    or not 1 <= lins[0].out_features <= MAX_RANK):
+                return None
+            layers.append((*(m.weight for m in lins), lins[-1].bias))
+        return layers
+
     def forward(self, x0):
+        layers = self._train_layers(x0)
+        if layers is not None:
+            from deeprec_amd.ops.fused_cross import cross_stack
+            return cross_stack(x0, layers)
         layers = self._fused_layers(x0)
         if layers is not None:
             from deeprec_amd.ops.fused_cross import cross_net
@@ -151,11 +188,12 @@ class DCN(RecModelBase):
 
     def __init__(self, embedding_dim=16, deep_sizes=(1024, 512, 256),
                  cross_layers=3, v2=False, device="cpu", bf16=True,
-                 fused_cross=False, **kw):
+                 fused_cross=False, fused_cross_train=False, **kw):
         name = "dcnv2" if v2 else "dcn"
         super().__init__(embedding_dim, device, bf16, name=name, **kw)
         in_dim = NUM_DENSE + self.num_sparse * embedding_dim
-        self.cross = _CrossNet(in_dim, cross_layers, v2, fused=fused_cross)
+        self.cross = _CrossNet(in_dim, cross_layers, v2, fused=fused_cross,
+                               fused_train=fused_cross_train)
         self.deep = make_mlp(deep_sizes, in_dim, device, self.bf16)
         self.head = nn.Linear(in_dim + deep_sizes[-1], 1)
         self.to(self.device_)
@@ -178,14 +216,15 @@ class MLPerfDLRMDCN(RecModelBase):
 
     def __init__(self, embedding_dim=16, bot_sizes=(128, 64, 16),
                  top_sizes=(512, 256), cross_layers=3, low_rank=32,
-                 device="cpu", bf16=True, **kw):
+                 device="cpu", bf16=True, fused_cross_train=False, **kw):
         super().__init__(embedding_dim, device, bf16,
                          name="mlperf_dlrm_dcn", **kw)
         assert bot_sizes[-1] == embedding_dim
         self.bot = make_mlp(bot_sizes, NUM_DENSE, device, self.bf16)
         in_dim = (self.num_sparse + 1) * embedding_dim
         self.cross = _CrossNet(in_dim, cross_layers, v2=True,
-                               low_rank=low_rank)
+                               low_rank=low_rank,
+                               fused_train=fused_cross_train)
         self.top = make_mlp(list(top_sizes) + [1], in_dim, device,
                             self.bf16, final_activation=False)
         self.to(self.device_)

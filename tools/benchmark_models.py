@@ -3,13 +3,18 @@ harness analog). Runs each model for a fixed step count on the current
 device and writes a markdown table.
 
 Usage: python tools/benchmark_models.py [--steps 30] [--out profiles/...]
-       [--static-seq] [--no-graph] [--fused-experts]
+       [--static-seq] [--no-graph] [--fused-experts] [--fused-cross-train]
 --static-seq builds din/dien/bst with static_seq=True (one padded lookup
 for sequence and target); din and bst then train as a captured hipGraph
 like the dense-feature models. dien stays eager: its auxiliary loss draws a
 permutation and branches on the host.
 --fused-experts builds mmoe and ple with fused_experts=True (grouped-expert
 kernels, ops/fused_moe.py); their rows are then named mmoe+fused, ple+fused.
+--fused-cross-train builds dcnv2 and mlperf_dlrm_dcn with
+fused_cross_train=True (one autograd node on the cross kernels,
+ops/fused_cross.py); their rows are then named dcnv2+fused,
+mlperf_dlrm_dcn+fused, and they step eagerly: that node has not been run
+under graph capture.
 Batch sizes follow the reference GPU benchmark config
 (modelzoo/benchmark/gpu/config.yaml: dlrm 8192, wide_and_deep 32768,
 deepfm 8192, dien 16384).
@@ -42,10 +47,12 @@ CAPTURABLE_SEQ = {"din", "bst"}
 
 
 FUSED_EXPERT_MODELS = {"mmoe", "ple"}
+FUSED_CROSS_MODELS = {"dcnv2", "mlperf_dlrm_dcn"}
 
 
 def bench_model(name, steps, warmup, device, use_graph=True,
-                static_seq=False, fused_experts=False):
+                static_seq=False, fused_experts=False,
+                fused_cross_train=False):
     from deeprec_amd.data.synthetic import CriteoSyntheticDataset
     from deeprec_amd.embedding.options import EmbeddingVariableOption
     from deeprec_amd.models import MODEL_REGISTRY, SEQUENCE_MODELS
@@ -53,7 +60,9 @@ def bench_model(name, steps, warmup, device, use_graph=True,
 
     torch.manual_seed(0)
     is_seq = name in SEQUENCE_MODELS
-    capturable = not is_seq or (static_seq and name in CAPTURABLE_SEQ)
+    fused_cross_train = fused_cross_train and name in FUSED_CROSS_MODELS
+    capturable = (not is_seq or (static_seq and name in CAPTURABLE_SEQ)
+                  ) and not fused_cross_train
     use_graph = use_graph and capturable and device.type == "cuda"
     batch = BATCH_SIZES.get(name, DEFAULT_BATCH)
     kw = {}
@@ -61,6 +70,8 @@ def bench_model(name, steps, warmup, device, use_graph=True,
         kw["static_seq"] = True
     if fused_experts and name in FUSED_EXPERT_MODELS:
         kw["fused_experts"] = True
+    if fused_cross_train:
+        kw["fused_cross_train"] = True
     if use_graph:
         kw["ev_option"] = EmbeddingVariableOption(init_capacity=1 << 23)
     m = MODEL_REGISTRY[name](device=device, bf16=device.type == "cuda",
@@ -144,6 +155,9 @@ def main():
     p.add_argument("--fused-experts", action="store_true",
                    help="mmoe and ple run their experts and gate mixture "
                         "on the grouped-expert kernels")
+    p.add_argument("--fused-cross-train", action="store_true",
+                   help="dcnv2 and mlperf_dlrm_dcn train their cross stack "
+                        "on the cross kernels, stepping eagerly")
     p.add_argument("--no-graph", action="store_true",
                    help="step eagerly even where capture is possible")
     args = p.parse_args()
@@ -159,8 +173,12 @@ def main():
                                          device,
                                          use_graph=not args.no_graph,
                                          static_seq=args.static_seq,
-                                         fused_experts=args.fused_experts)
-            if args.fused_experts and name in FUSED_EXPERT_MODELS:
+                                         fused_experts=args.fused_experts,
+                                         fused_cross_train=args
+                                         .fused_cross_train)
+            if (args.fused_experts and name in FUSED_EXPERT_MODELS
+                    or args.fused_cross_train
+                    and name in FUSED_CROSS_MODELS):
                 name += "+fused"
             rows.append((name, batch, sps, ms))
             print(f"{name:18s} batch={batch:6d}  {sps:12.0f} samples/s  "
