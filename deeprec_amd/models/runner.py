@@ -113,6 +113,9 @@ def build_argparser():
     p.add_argument("--fused_cross_train", action="store_true",
                    help="dcnv2 / mlperf_dlrm_dcn: train the cross stack as "
                         "one autograd node on the cross kernels")
+    p.add_argument("--fused_mask_blocks", action="store_true",
+                   help="masknet: run the mask generators and blocks on "
+                        "the MFMA linear and mask-block kernels")
     p.add_argument("--eval_steps", type=int, default=0,
                    help="after training, evaluate N batches (no inserts, "
                         "no training) and print loss/accuracy/AUC — the "
@@ -147,9 +150,9 @@ def make_ev_option(args) -> EmbeddingVariableOption:
 
 
 def width_kwargs(args) -> dict:
-    """--gru_hidden / --item_dim / --fused_experts / --fused_cross_train as
-    constructor keywords: only those given, and only for a model whose
-    constructor names them."""
+    """--gru_hidden / --item_dim / --fused_experts / --fused_cross_train /
+    --fused_mask_blocks as constructor keywords: only those given, and only
+    for a model whose constructor names them."""
     params = inspect.signature(MODEL_REGISTRY[args.model]).parameters
     kw = {}
     for name in ("gru_hidden", "item_dim"):
@@ -160,13 +163,15 @@ def width_kwargs(args) -> dict:
             raise SystemExit(f"--{name} does not apply to --model "
                              f"{args.model}")
         kw[name] = value
-    for name in ("fused_experts", "fused_cross_train"):
+    for name, key in (("fused_experts", "fused_experts"),
+                      ("fused_cross_train", "fused_cross_train"),
+                      ("fused_mask_blocks", "fused_blocks")):
         if not getattr(args, name):
             continue
-        if name not in params:
+        if key not in params:
             raise SystemExit(f"--{name} does not apply to --model "
                              f"{args.model}")
-        kw[name] = True
+        kw[key] = True
     return kw
 
 
@@ -368,6 +373,11 @@ def main(argv=None):
             print(f"EVAL model={args.model} steps={args.eval_steps} "
                   f"loss={sum(losses) / len(losses):.4f} "
                   f"accuracy={acc.result():.4f} auc={auc.result():.4f}")
+    if hasattr(batches, "close"):
+        # stop the staging thread before the interpreter goes down: a daemon
+        # thread that is still inside a GPU call then aborts the process
+        batches.close()
+        batches.thread.join(timeout=10)
     if world > 1:
         import torch.distributed as dist
         dist.destroy_process_group()

@@ -487,11 +487,20 @@ class PLE(RecModelBase):
 
 class MaskNet(RecModelBase):
     """MaskNet serial model: instance-guided masks over feature embedding
-    (reference: modelzoo/masknet)."""
+    (reference: modelzoo/masknet).
+
+    fused_blocks=True runs, on the GPU, every mask generator as two bf16
+    MFMA linear layers and every block as one autograd node on the
+    mask-block kernels (ops/fused_mask.py: mask_block), with x0 cast to
+    bf16 once; off the GPU, or when a generator or block is no longer
+    plain nn.Linear / nn.LayerNorm (fp8-converted layers), it takes the
+    default path. Parameters and state_dict keys are the same either
+    way."""
 
     def __init__(self, embedding_dim=16, n_blocks=3, hidden=256,
-                 device="cpu", bf16=True, **kw):
+                 device="cpu", bf16=True, fused_blocks=False, **kw):
         super().__init__(embedding_dim, device, bf16, name="masknet", **kw)
+        self.fused_blocks = fused_blocks
         in_dim = NUM_DENSE + self.num_sparse * embedding_dim
         self.ln = nn.LayerNorm(in_dim)
         self.mask_gens = nn.ModuleList()
@@ -510,7 +519,28 @@ class MaskNet(RecModelBase):
     def forward(self, dense, sparse_ids, train=True):
         emb = self.sparse_feats(sparse_ids, train).float()
         x0 = self.ln(torch.cat([dense, emb.flatten(1)], 1))
+        if self.fused_blocks and self._fused_ok(x0):
+            return self._forward_fused(x0)
         h = x0
         for gen, blk in zip(self.mask_gens, self.blocks):
             h = blk(gen(x0) * h)
         return self.head(h).squeeze(1)
+
+    def _fused_ok(self, x0):
+        return x0.device.type == "cuda" and all(
+            type(m) is nn.Linear
+            for gen, blk in zip(self.mask_gens, self.blocks)
+            for m in (gen[0], gen[2], blk[0]))
+
+    def _forward_fused(self, x0):
+        from deeprec_amd.ops.fused_mask import mask_block
+        from deeprec_amd.ops.fused_mlp import _ACT_ID, _FusedLinear
+        x16 = x0.to(torch.bfloat16)
+        h = x16
+        for gen, blk in zip(self.mask_gens, self.blocks):
+            t = _FusedLinear.apply(x16, gen[0].weight, gen[0].bias,
+                                   _ACT_ID["relu"])
+            mask = _FusedLinear.apply(t, gen[2].weight, gen[2].bias,
+                                      _ACT_ID["none"])
+            h = mask_block(h, mask, blk[0], blk[1])
+        return self.head(h.float()).squeeze(1)

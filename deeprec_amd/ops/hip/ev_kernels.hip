@@ -1601,6 +1601,7 @@ void register_ev_apply(pybind11::module_& mod);   // ev_apply_kernels.hip
 void register_loss(pybind11::module_& mod);       // loss_kernels.hip
 void register_cross(pybind11::module_& mod);      // cross_kernels.hip
 void register_moe(pybind11::module_& mod);        // moe_kernels.hip
+void register_mask(pybind11::module_& mod);       // mask_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_dense(mod);
@@ -1612,6 +1613,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_loss(mod);
   register_cross(mod);
   register_moe(mod);
+  register_mask(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);

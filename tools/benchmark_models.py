@@ -4,6 +4,7 @@ device and writes a markdown table.
 
 Usage: python tools/benchmark_models.py [--steps 30] [--out profiles/...]
        [--static-seq] [--no-graph] [--fused-experts] [--fused-cross-train]
+       [--fused-mask-blocks]
 --static-seq builds din/dien/bst with static_seq=True (one padded lookup
 for sequence and target); din and bst then train as a captured hipGraph
 like the dense-feature models. dien stays eager: its auxiliary loss draws a
@@ -15,6 +16,8 @@ fused_cross_train=True (one autograd node on the cross kernels,
 ops/fused_cross.py); their rows are then named dcnv2+fused,
 mlperf_dlrm_dcn+fused, and they step eagerly: that node has not been run
 under graph capture.
+--fused-mask-blocks builds masknet with fused_blocks=True (mask-block
+kernels, ops/fused_mask.py); its row is then named masknet+fused.
 Batch sizes follow the reference GPU benchmark config
 (modelzoo/benchmark/gpu/config.yaml: dlrm 8192, wide_and_deep 32768,
 deepfm 8192, dien 16384).
@@ -48,11 +51,12 @@ CAPTURABLE_SEQ = {"din", "bst"}
 
 FUSED_EXPERT_MODELS = {"mmoe", "ple"}
 FUSED_CROSS_MODELS = {"dcnv2", "mlperf_dlrm_dcn"}
+FUSED_MASK_MODELS = {"masknet"}
 
 
 def bench_model(name, steps, warmup, device, use_graph=True,
                 static_seq=False, fused_experts=False,
-                fused_cross_train=False):
+                fused_cross_train=False, fused_mask_blocks=False):
     from deeprec_amd.data.synthetic import CriteoSyntheticDataset
     from deeprec_amd.embedding.options import EmbeddingVariableOption
     from deeprec_amd.models import MODEL_REGISTRY, SEQUENCE_MODELS
@@ -72,6 +76,8 @@ def bench_model(name, steps, warmup, device, use_graph=True,
         kw["fused_experts"] = True
     if fused_cross_train:
         kw["fused_cross_train"] = True
+    if fused_mask_blocks and name in FUSED_MASK_MODELS:
+        kw["fused_blocks"] = True
     if use_graph:
         kw["ev_option"] = EmbeddingVariableOption(init_capacity=1 << 23)
     m = MODEL_REGISTRY[name](device=device, bf16=device.type == "cuda",
@@ -158,6 +164,9 @@ def main():
     p.add_argument("--fused-cross-train", action="store_true",
                    help="dcnv2 and mlperf_dlrm_dcn train their cross stack "
                         "on the cross kernels, stepping eagerly")
+    p.add_argument("--fused-mask-blocks", action="store_true",
+                   help="masknet runs its mask generators and blocks on "
+                        "the MFMA linear and mask-block kernels")
     p.add_argument("--no-graph", action="store_true",
                    help="step eagerly even where capture is possible")
     args = p.parse_args()
@@ -175,10 +184,14 @@ def main():
                                          static_seq=args.static_seq,
                                          fused_experts=args.fused_experts,
                                          fused_cross_train=args
-                                         .fused_cross_train)
+                                         .fused_cross_train,
+                                         fused_mask_blocks=args
+                                         .fused_mask_blocks)
             if (args.fused_experts and name in FUSED_EXPERT_MODELS
                     or args.fused_cross_train
-                    and name in FUSED_CROSS_MODELS):
+                    and name in FUSED_CROSS_MODELS
+                    or args.fused_mask_blocks
+                    and name in FUSED_MASK_MODELS):
                 name += "+fused"
             rows.append((name, batch, sps, ms))
             print(f"{name:18s} batch={batch:6d}  {sps:12.0f} samples/s  "
