@@ -194,12 +194,13 @@ class FusedLinear(nn.Module):
 
 class _DotInteraction(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, feats, p_pad):
+    def forward(ctx, feats, p_pad, variant):
         from deeprec_amd.ops.build_ext import require_extension
         ext = require_extension()
         f16 = feats.to(torch.bfloat16).contiguous()
-        out = ext.interact_fwd(f16, p_pad)
+        out = ext.interact_fwd(f16, p_pad, variant)
         ctx.ext = ext
+        ctx.variant = variant
         ctx.f_dtype = feats.dtype
         ctx.save_for_backward(f16)
         return out
@@ -207,18 +208,22 @@ class _DotInteraction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         (f16,) = ctx.saved_tensors
-        df = ctx.ext.interact_bwd(grad_out.to(torch.bfloat16), f16)
-        return df.to(ctx.f_dtype), None
+        df = ctx.ext.interact_bwd(grad_out.to(torch.bfloat16), f16,
+                                  ctx.variant)
+        return df.to(ctx.f_dtype), None, None
 
 
-def dot_interaction(feats: torch.Tensor, p_pad: int = None) -> torch.Tensor:
+def dot_interaction(feats: torch.Tensor, p_pad: int = None,
+                    variant: int = 0) -> torch.Tensor:
     """feats [B, F, D] -> pairwise dots [B, p_pad] (i<j upper triangle,
-    zero-padded). Fused gfx950 kernel on GPU; torch fallback elsewhere."""
+    zero-padded). Fused gfx950 kernel on GPU; torch fallback elsewhere.
+    variant (GPU only): 0 = MFMA kernels where the shape allows, 1 = scalar
+    kernels, 2 = MFMA kernels or an error."""
     b, f, d = feats.shape
     p = f * (f - 1) // 2
     p_pad = p_pad or p
     if feats.device.type == "cuda" and (f * d) % 8 == 0:
-        return _DotInteraction.apply(feats, p_pad)
+        return _DotInteraction.apply(feats, p_pad, variant)
     z = torch.bmm(feats.float(), feats.float().transpose(1, 2))
     iu = torch.triu_indices(f, f, offset=1, device=feats.device)
     out = z[:, iu[0], iu[1]]
@@ -229,13 +234,14 @@ def dot_interaction(feats: torch.Tensor, p_pad: int = None) -> torch.Tensor:
 
 class _DotInteractionCat(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, bot, emb, p_pad):
+    def forward(ctx, bot, emb, p_pad, variant):
         from deeprec_amd.ops.build_ext import require_extension
         ext = require_extension()
         b16 = bot.to(torch.bfloat16).contiguous()
         e16 = emb.to(torch.bfloat16).contiguous()
-        out = ext.interact_cat_fwd(b16, e16, p_pad)
+        out = ext.interact_cat_fwd(b16, e16, p_pad, variant)
         ctx.ext = ext
+        ctx.variant = variant
         ctx.dtypes = (bot.dtype, emb.dtype)
         ctx.save_for_backward(b16, e16)
         return out
@@ -244,19 +250,20 @@ class _DotInteractionCat(torch.autograd.Function):
     def backward(ctx, grad_out):
         b16, e16 = ctx.saved_tensors
         dbot, demb = ctx.ext.interact_cat_bwd(
-            grad_out.to(torch.bfloat16), b16, e16)
+            grad_out.to(torch.bfloat16), b16, e16, ctx.variant)
         bd, ed = ctx.dtypes
-        return dbot.to(bd), demb.to(ed), None
+        return dbot.to(bd), demb.to(ed), None, None
 
 
 def dot_interaction_cat(bot: torch.Tensor, emb: torch.Tensor,
-                        p_pad: int) -> torch.Tensor:
+                        p_pad: int, variant: int = 0) -> torch.Tensor:
     """bot [B,D] + emb [B,F,D] -> [B, D + p_pad] = [bot | pairwise dots
     over [bot; emb] rows, i<j upper triangle, zero-padded] in ONE fused
     kernel per direction — removes the feats-assembly cat AND the
-    top-MLP input cat. Torch fallback composes the same math."""
+    top-MLP input cat. Torch fallback composes the same math. `variant`
+    as in dot_interaction."""
     if bot.device.type == "cuda" and bot.shape[1] % 8 == 0:
-        out = _DotInteractionCat.apply(bot, emb, p_pad)
+        out = _DotInteractionCat.apply(bot, emb, p_pad, variant)
         # keep the caller's compute dtype (the fp32 debug path feeds
         # plain nn.Linear layers)
         return out if out.dtype == bot.dtype else out.to(bot.dtype)

@@ -1267,13 +1267,41 @@ torch::Tensor act_bwd(torch::Tensor dy, torch::Tensor out, int64_t act) {
   return g;
 }
 
-torch::Tensor interact_fwd(torch::Tensor feats, int64_t p_pad) {
+// The D == 16, F <= 32 shapes run on MFMA (interact_kernels.hip).
+bool interact_mfma_eligible(int64_t F, int64_t D, int64_t p_pad);
+void interact_mfma_fwd_launch(const short* x0, const short* emb, int B, int F,
+                              int p_pad, short* out);
+void interact_mfma_bwd_launch(const short* grad, const short* x0,
+                              const short* emb, int B, int F, int p_pad,
+                              short* dx0, short* demb);
+
+// variant: 0 = MFMA where the shape is eligible, 1 = the scalar kernels,
+// 2 = MFMA, an error where the shape is not eligible.
+static bool interact_use_mfma(const char* op, int64_t variant, int64_t F,
+                              int64_t D, int64_t p_pad) {
+  TORCH_CHECK(variant >= 0 && variant <= 2, op, ": variant must be 0 "
+              "(automatic), 1 (scalar) or 2 (MFMA), got ", variant);
+  const bool ok = interact_mfma_eligible(F, D, p_pad);
+  TORCH_CHECK(variant != 2 || ok, op, ": the MFMA kernels need D == 16, "
+              "2 <= F <= 32 and p_pad a multiple of 8 in [P, 1024]; got F = ",
+              F, ", D = ", D, ", p_pad = ", p_pad);
+  return variant != 1 && ok;
+}
+
+torch::Tensor interact_fwd(torch::Tensor feats, int64_t p_pad,
+                           int64_t variant) {
   TORCH_CHECK(feats.scalar_type() == torch::kBFloat16 &&
               feats.is_contiguous());
   int B = feats.size(0), F = feats.size(1), D = feats.size(2);
   int P = F * (F - 1) / 2;
   TORCH_CHECK((F * D) % 8 == 0, "F*D must be a multiple of 8");
+  const bool mfma = interact_use_mfma("interact_fwd", variant, F, D, p_pad);
   auto out = torch::empty({B, p_pad}, feats.options());
+  if (mfma) {
+    interact_mfma_fwd_launch(bf_ptr(feats), nullptr, B, F, (int)p_pad,
+                             bf_ptr_mut(out));
+    return out;
+  }
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)F * D * sizeof(short);
   k_interact_fwd<<<blocks, 256, lds, current_hip_stream()>>>(
@@ -1281,11 +1309,21 @@ torch::Tensor interact_fwd(torch::Tensor feats, int64_t p_pad) {
   return out;
 }
 
-torch::Tensor interact_bwd(torch::Tensor grad, torch::Tensor feats) {
+torch::Tensor interact_bwd(torch::Tensor grad, torch::Tensor feats,
+                           int64_t variant) {
   int B = feats.size(0), F = feats.size(1), D = feats.size(2);
-  TORCH_CHECK(F <= 40, "interact_bwd: pair LUT supports F <= 40");
   int P = F * (F - 1) / 2;
   int P_pad = grad.size(1);
+  if (interact_use_mfma("interact_bwd", variant, F, D, P_pad)) {
+    TORCH_CHECK(feats.scalar_type() == torch::kBFloat16 &&
+                feats.is_contiguous() && grad.size(0) == B);
+    auto dfeats = torch::empty_like(feats);
+    interact_mfma_bwd_launch(bf_ptr(grad.contiguous()), bf_ptr(feats),
+                             nullptr, B, F, P_pad, bf_ptr_mut(dfeats),
+                             nullptr);
+    return dfeats;
+  }
+  TORCH_CHECK(F <= 40, "interact_bwd: pair LUT supports F <= 40");
   auto dfeats = torch::empty_like(feats);
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)(F * D + ((P + 7) & ~7)) * sizeof(short);
@@ -1296,14 +1334,23 @@ torch::Tensor interact_bwd(torch::Tensor grad, torch::Tensor feats) {
 }
 
 torch::Tensor interact_cat_fwd(torch::Tensor bot, torch::Tensor emb,
-                               int64_t p_pad) {
+                               int64_t p_pad, int64_t variant) {
   TORCH_CHECK(bot.scalar_type() == torch::kBFloat16 && bot.is_contiguous());
   TORCH_CHECK(emb.scalar_type() == torch::kBFloat16 && emb.is_contiguous());
   int B = emb.size(0), Fe = emb.size(1), D = emb.size(2);
   int F = Fe + 1;
   int P = F * (F - 1) / 2;
   TORCH_CHECK(D % 8 == 0, "D must be a multiple of 8");
+  const bool mfma =
+      interact_use_mfma("interact_cat_fwd", variant, F, D, p_pad);
   auto out = torch::empty({B, D + p_pad}, emb.options());
+  if (mfma) {
+    TORCH_CHECK(bot.dim() == 2 && bot.size(0) == B && bot.size(1) == D,
+                "interact_cat_fwd: bot must be [B, D]");
+    interact_mfma_fwd_launch(bf_ptr(bot), bf_ptr(emb), B, F, (int)p_pad,
+                             bf_ptr_mut(out));
+    return out;
+  }
   int blocks = (B + 3) / 4;
   size_t lds = 4 * (size_t)F * D * sizeof(short);
   k_interact_cat_fwd<<<blocks, 256, lds, current_hip_stream()>>>(
@@ -1312,12 +1359,26 @@ torch::Tensor interact_cat_fwd(torch::Tensor bot, torch::Tensor emb,
 }
 
 std::tuple<torch::Tensor, torch::Tensor> interact_cat_bwd(
-    torch::Tensor grad, torch::Tensor bot, torch::Tensor emb) {
+    torch::Tensor grad, torch::Tensor bot, torch::Tensor emb,
+    int64_t variant) {
   int B = emb.size(0), Fe = emb.size(1), D = emb.size(2);
   int F = Fe + 1;
-  TORCH_CHECK(F <= 40, "interact: pair LUT supports F <= 40");
   int P = F * (F - 1) / 2;
   int P_pad = grad.size(1) - D;
+  if (interact_use_mfma("interact_cat_bwd", variant, F, D, P_pad)) {
+    TORCH_CHECK(bot.scalar_type() == torch::kBFloat16 &&
+                bot.is_contiguous() && bot.dim() == 2 && bot.size(0) == B &&
+                bot.size(1) == D && grad.size(0) == B);
+    TORCH_CHECK(emb.scalar_type() == torch::kBFloat16 &&
+                emb.is_contiguous());
+    auto dbot = torch::empty_like(bot);
+    auto demb = torch::empty_like(emb);
+    interact_mfma_bwd_launch(bf_ptr(grad.contiguous()), bf_ptr(bot),
+                             bf_ptr(emb), B, F, P_pad, bf_ptr_mut(dbot),
+                             bf_ptr_mut(demb));
+    return {dbot, demb};
+  }
+  TORCH_CHECK(F <= 40, "interact: pair LUT supports F <= 40");
   auto dbot = torch::empty_like(bot);
   auto demb = torch::empty_like(emb);
   int blocks = (B + 3) / 4;
@@ -1352,10 +1413,14 @@ torch::Tensor l2norm_bwd(torch::Tensor dy, torch::Tensor y,
 void register_dense(py::module_& mod) {
   mod.def("l2norm_fwd", &l2norm_fwd);
   mod.def("l2norm_bwd", &l2norm_bwd);
-  mod.def("interact_fwd", &interact_fwd);
-  mod.def("interact_bwd", &interact_bwd);
-  mod.def("interact_cat_fwd", &interact_cat_fwd);
-  mod.def("interact_cat_bwd", &interact_cat_bwd);
+  mod.def("interact_fwd", &interact_fwd, py::arg("feats"), py::arg("p_pad"),
+          py::arg("variant") = 0);
+  mod.def("interact_bwd", &interact_bwd, py::arg("grad"), py::arg("feats"),
+          py::arg("variant") = 0);
+  mod.def("interact_cat_fwd", &interact_cat_fwd, py::arg("bot"),
+          py::arg("emb"), py::arg("p_pad"), py::arg("variant") = 0);
+  mod.def("interact_cat_bwd", &interact_cat_bwd, py::arg("grad"),
+          py::arg("bot"), py::arg("emb"), py::arg("variant") = 0);
   mod.def("linear_fwd", &linear_fwd, py::arg("x"), py::arg("w"),
           py::arg("bias"), py::arg("act"), py::arg("variant") = -1);
   mod.def("linear_dx", &linear_dx, py::arg("g"), py::arg("w"),
