@@ -18,7 +18,10 @@
 //   fwd: operands straight from L2 (weights are L2-resident, A rows
 //        stream); 64x64 block tiles maximize block count. A K step's
 //        fragment loads are branch-free and issued together, the next
-//        step's before this step's MFMAs (register double buffer).
+//        step's before this step's MFMAs (register double buffer). The
+//        wide layers instead stage both operands per 64-wide K chunk in
+//        swizzled LDS tiles, loaded once per block as full 128-B rows
+//        (k_linear_fwd_lds).
 //   dX:  W columns are strided -> W tile staged row-major in LDS and read
 //        with the transposed LDS read for the wide-N layers
 //        (k_linear_dx_lds), direct for narrow ones.
@@ -176,28 +179,21 @@ __device__ __forceinline__ void dbias_reduce_add(float bsum, int lane, int n0,
 // 8192x512x480 — fewer blocks cost more than the halved A re-reads.)
 // The K loop is fwd_accumulate in mfma_fwd.h.
 // ------------------------------------------------------------------
+constexpr int FWD_CSTAGE_COLS = 72;  // 64 + 8 (bank de-phase)
+
+// Epilogue of a wave's 16*MT x 64 tile at (m0, n0), m0 < M: bias,
+// activation, bf16 store. cstage is this wave's own [16][FWD_CSTAGE_COLS]
+// LDS tile; no other wave may touch it while the call runs.
 template <int MT>
-__global__ void __launch_bounds__(256) k_linear_fwd_t(const short* __restrict__ A,
-                               const short* __restrict__ W,
-                               const float* __restrict__ bias, int M, int N,
-                               int K, int act, short* __restrict__ C) {
-  const int lane = threadIdx.x & 63;
-  const int wave = threadIdx.x >> 6;
-  const int ntiles64 = (N + 63) / 64;
-  const int m0 = (blockIdx.x / ntiles64) * 64 * MT + wave * 16 * MT;
-  const int n0 = (blockIdx.x % ntiles64) * 64;
-  if (m0 >= M) return;
-  f32x4 acc[MT][4] = {};
+__device__ __forceinline__ void fwd_store_tile(
+    const f32x4 (&acc)[MT][4], short (*cstage)[FWD_CSTAGE_COLS], int lane,
+    int m0, int n0, int M, int N, const float* __restrict__ bias, int act,
+    short* __restrict__ C) {
   const int nt = min(4, (N - n0 + 15) / 16);
-  if (m0 + 16 * MT <= M && n0 + 64 <= N)  // wave-uniform
-    fwd_accumulate<MT, false>(A, W, M, N, K, m0, n0, lane, acc);
-  else
-    fwd_accumulate<MT, true>(A, W, M, N, K, m0, n0, lane, acc);
   // D: col = lane%16, row = 4*(lane/16) + i. The MFMA output layout
   // writes 32B fragments per instruction; for FULL 16x64 tiles, stage
   // the tile in LDS and flush 128B row bursts (the fragmented stores
   // capped this kernel at ~520 GB/s on an 8 MB output).
-  __shared__ short cstage[4][16][72];  // 72 = 64 + 8 (bank de-phase)
   const bool full_tile =
       (MT == 1) && (n0 + 64 <= N) && (m0 + 16 <= M) && ((N & 7) == 0);
   if (full_tile) {
@@ -207,8 +203,7 @@ __global__ void __launch_bounds__(256) k_linear_fwd_t(const short* __restrict__ 
       const float bv = bias ? bias[n0 + cn] : 0.0f;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        cstage[wave][(lane >> 4) * 4 + i][cn] =
-            fwd_act_u16(acc[0][t][i], bv, act);
+        cstage[(lane >> 4) * 4 + i][cn] = fwd_act_u16(acc[0][t][i], bv, act);
       }
     }
     __builtin_amdgcn_s_waitcnt(0);  // LDS writes visible within the wave
@@ -220,7 +215,7 @@ __global__ void __launch_bounds__(256) k_linear_fwd_t(const short* __restrict__ 
       const int c8 = (lane & 7) * 8;
       bf16x8 vreg;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) vreg[j] = cstage[wave][row][c8 + j];
+      for (int j = 0; j < 8; ++j) vreg[j] = cstage[row][c8 + j];
       *reinterpret_cast<bf16x8*>(
           C + (int64_t)(m0 + row) * N + n0 + c8) = vreg;
     }
@@ -242,6 +237,161 @@ __global__ void __launch_bounds__(256) k_linear_fwd_t(const short* __restrict__ 
       }
     }
   }
+}
+
+template <int MT>
+__global__ void __launch_bounds__(256) k_linear_fwd_t(const short* __restrict__ A,
+                               const short* __restrict__ W,
+                               const float* __restrict__ bias, int M, int N,
+                               int K, int act, short* __restrict__ C) {
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int ntiles64 = (N + 63) / 64;
+  const int m0 = (blockIdx.x / ntiles64) * 64 * MT + wave * 16 * MT;
+  const int n0 = (blockIdx.x % ntiles64) * 64;
+  if (m0 >= M) return;
+  f32x4 acc[MT][4] = {};
+  if (m0 + 16 * MT <= M && n0 + 64 <= N)  // wave-uniform
+    fwd_accumulate<MT, false>(A, W, M, N, K, m0, n0, lane, acc);
+  else
+    fwd_accumulate<MT, true>(A, W, M, N, K, m0, n0, lane, acc);
+  __shared__ short cstage[4][16][FWD_CSTAGE_COLS];
+  fwd_store_tile<MT>(acc, cstage[wave], lane, m0, n0, M, N, bias, act, C);
+}
+
+// ------------------------------------------------------------------
+// fwd with block-staged operands, for K % 8 == 0: the same 64 x 64 block
+// tile, 16 x 64 wave tile, MFMAs in the same ascending-k order and the same
+// epilogue as k_linear_fwd_t<1>, so the outputs are bit-identical; only the
+// fragments come from LDS. There each of the four waves fetches the
+// block's whole 64 x 32 W slice per K step, as 16-B pieces of 16 different
+// rows per load instruction (half-used 128-B lines). Here the block loads
+// A[64][64] and W[64][64] once per 64-wide K chunk, 8 lanes per 128-B row.
+//
+// Tiles are row-major [64][64] bf16, 128-B rows, no padding; the 16-B
+// piece index is XORed with (row >> 1) & 7. A fragment read takes, per 16
+// lanes, rows r..r+15 at one piece p: row parity picks the half of the 64
+// banks, p ^ ((row >> 1) & 7) one of its eight 16-B slots, so the 16 rows
+// tile all 64 banks. A store takes, per 8 lanes, the eight pieces of one
+// row: a permutation of 128 contiguous bytes.
+//
+// Pipeline: two buffers; chunk c+1's global loads are issued into
+// registers before chunk c's LDS reads and MFMAs and stored to the other
+// buffer after them; one barrier per chunk. Rows past M or N are read from
+// the clamped last row, pieces past K from column 0 of their row, and both
+// are replaced by zeros with a select before the LDS store (never a
+// multiply: the source may hold NaN). EVERY wave runs every barrier: a
+// wave past M only skips its stores.
+// ------------------------------------------------------------------
+constexpr int FL_K = 64;             // K chunk
+constexpr int FL_TILE = 64 * FL_K;   // elements of one staged operand tile
+
+__device__ __forceinline__ int fl_off(int row, int piece) {
+  return row * FL_K + ((piece ^ ((row >> 1) & 7)) << 3);
+}
+
+__global__ void __launch_bounds__(256) k_linear_fwd_lds(
+    const short* __restrict__ A, const short* __restrict__ W,
+    const float* __restrict__ bias, int M, int N, int K, int act,
+    short* __restrict__ C) {
+  // [buffer][A tile, W tile]; the epilogue's cstage reuses buffer 0
+  __shared__ __attribute__((aligned(16))) short tiles[2][2 * FL_TILE];
+  static_assert(sizeof(short) * 4 * 16 * FWD_CSTAGE_COLS <=
+                    sizeof(short) * 2 * FL_TILE,
+                "cstage must fit in one buffer");
+  const int lane = threadIdx.x & 63;
+  const int wave = threadIdx.x >> 6;
+  const int ntiles64 = (N + 63) / 64;
+  const int mb = (blockIdx.x / ntiles64) * 64;
+  const int n0 = (blockIdx.x % ntiles64) * 64;
+  const int m0 = mb + wave * 16;
+
+  // staging: thread -> 16-B piece tid % 8 of rows tid / 8 and tid / 8 + 32
+  // of both tiles (q = 0, 1: A; 2, 3: W)
+  const int piece = threadIdx.x & 7;
+  const short* gp[4];
+  bool ok[4];
+  int soff[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int trow = (threadIdx.x >> 3) + (q & 1) * 32;
+    const bool is_w = q >= 2;
+    const int row = (is_w ? n0 : mb) + trow;
+    const int rows = is_w ? N : M;
+    ok[q] = row < rows;
+    gp[q] = (is_w ? W : A) + (int64_t)min(row, rows - 1) * K;
+    soff[q] = (is_w ? FL_TILE : 0) + fl_off(trow, piece);
+  }
+  bf16x8 st[4];
+  auto load = [&](int c) {
+    const int kc = c * FL_K + piece * 8;
+    const int col = kc < K ? kc : 0;  // K % 8 == 0: wholly inside or outside
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      st[q] = *reinterpret_cast<const bf16x8_u*>(gp[q] + col);
+    // keep the loads ahead of the MFMAs they are meant to overlap
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  auto store = [&](int c) {
+    const bool kin = c * FL_K + piece * 8 < K;
+    const bf16x8 zero = {};
+    short* buf = tiles[c & 1];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+      *reinterpret_cast<bf16x8*>(buf + soff[q]) =
+          (ok[q] && kin) ? st[q] : zero;
+  };
+
+  // fragment reads: row = lane % 16 of the wave's A rows / of W tile t,
+  // piece 4 * step + lane / 16; (row >> 1) & 7 is the same for all of them
+  const int frow = lane & 15;
+  const int fsw = frow >> 1;
+  const int a_base = (wave * 16 + frow) * FL_K;
+  const int b_base = FL_TILE + frow * FL_K;
+  int koff[2];
+#pragma unroll
+  for (int s = 0; s < 2; ++s) koff[s] = ((4 * s + (lane >> 4)) ^ fsw) << 3;
+
+  f32x4 acc[1][4] = {};
+  const int nchunks = (K + FL_K - 1) / FL_K;  // block-uniform
+  auto step = [&](const short* cur, int s) {
+    const bf16x8 a = *reinterpret_cast<const bf16x8*>(cur + a_base + koff[s]);
+    bf16x8 b[4];
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      b[t] = *reinterpret_cast<const bf16x8*>(cur + b_base + t * 16 * FL_K +
+                                              koff[s]);
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+      acc[0][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[t], acc[0][t],
+                                                          0, 0, 0);
+  };
+  if (nchunks > 0) {
+    load(0);
+    store(0);
+    int c = 0;
+    // every chunk but the last: both steps, a successor, no branch
+    for (; c + 1 < nchunks; ++c) {
+      // chunk c's stores are visible, and every wave has finished reading
+      // the other buffer (chunk c - 1)
+      __syncthreads();
+      load(c + 1);
+      step(tiles[c & 1], 0);
+      step(tiles[c & 1], 1);
+      // and the wait for the loads behind the MFMAs
+      __builtin_amdgcn_sched_barrier(0);
+      store(c + 1);
+    }
+    __syncthreads();
+    step(tiles[c & 1], 0);
+    // the last chunk's second step may lie wholly past K: not a step at all
+    if (c * FL_K + 32 < K) step(tiles[c & 1], 1);
+  }
+  __syncthreads();  // all reads done before buffer 0 becomes cstage
+  if (m0 >= M) return;  // after the last barrier
+  fwd_store_tile<1>(
+      acc, reinterpret_cast<short(*)[FWD_CSTAGE_COLS]>(tiles[0]) + wave * 16,
+      lane, m0, n0, M, N, bias, act, C);
 }
 
 // ------------------------------------------------------------------
@@ -1011,33 +1161,75 @@ static void check_bf16_matrix(const torch::Tensor& t, const char* op,
               " must be contiguous (row-major)");
 }
 
-torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w_bf16,
-                         torch::Tensor bias, int64_t act,
-                         int64_t variant) {
-  check_bf16_matrix(x, "linear_fwd", "x");
-  check_bf16_matrix(w_bf16, "linear_fwd", "w");
-  TORCH_CHECK(x.size(1) == w_bf16.size(1), "linear_fwd: x is [M,",
-              x.size(1), "] but w is [N,", w_bf16.size(1), "]");
-  int M = x.size(0), K = x.size(1), N = w_bf16.size(0);
+static void check_fwd_operands(const char* op, const torch::Tensor& x,
+                               const torch::Tensor& w_bf16,
+                               const torch::Tensor& bias) {
+  check_bf16_matrix(x, op, "x");
+  check_bf16_matrix(w_bf16, op, "w");
+  TORCH_CHECK(x.size(1) == w_bf16.size(1), op, ": x is [M,", x.size(1),
+              "] but w is [N,", w_bf16.size(1), "]");
   TORCH_CHECK(!bias.defined() || bias.numel() == 0 ||
-                  (bias.numel() == N && bias.is_contiguous()),
-              "linear_fwd: bias must be empty or contiguous [N]");
-  TORCH_CHECK(variant >= -1 && variant <= 1, "linear_fwd: variant must be "
-              "-1 (automatic), 0 (MT=1) or 1 (MT=2), got ", variant);
+                  (bias.numel() == w_bf16.size(0) && bias.is_contiguous()),
+              op, ": bias must be empty or contiguous [N]");
+}
+
+enum class FwdKernel { MT1, MT2, LDS };
+
+static torch::Tensor linear_fwd_launch(FwdKernel kernel,
+                                       const torch::Tensor& x,
+                                       const torch::Tensor& w_bf16,
+                                       const torch::Tensor& bias,
+                                       int64_t act) {
+  int M = x.size(0), K = x.size(1), N = w_bf16.size(0);
   auto out = torch::empty({M, N}, x.options());
   int tiles_n = (N + 63) / 64;
   const float* bp =
       bias.defined() && bias.numel() ? bias.data_ptr<float>() : nullptr;
-  if (variant == 1) {
-    int blocks = ((M + 127) / 128) * tiles_n;
+  int blocks = ((M + 63) / 64) * tiles_n;
+  if (kernel == FwdKernel::MT2) {
+    blocks = ((M + 127) / 128) * tiles_n;
     k_linear_fwd_t<2><<<blocks, 256, 0, current_hip_stream()>>>(
         bf_ptr(x), bf_ptr(w_bf16), bp, M, N, K, (int)act, bf_ptr_mut(out));
-  } else {  // -1, 0: MT=1 measured fastest across the zoo
-    int blocks = ((M + 63) / 64) * tiles_n;
+  } else if (kernel == FwdKernel::LDS) {
+    k_linear_fwd_lds<<<blocks, 256, 0, current_hip_stream()>>>(
+        bf_ptr(x), bf_ptr(w_bf16), bp, M, N, K, (int)act, bf_ptr_mut(out));
+  } else {
     k_linear_fwd_t<1><<<blocks, 256, 0, current_hip_stream()>>>(
         bf_ptr(x), bf_ptr(w_bf16), bp, M, N, K, (int)act, bf_ptr_mut(out));
   }
   return out;
+}
+
+// Where variant -1 takes k_linear_fwd_lds instead of k_linear_fwd_t<1>:
+// the (N, K) range in which it measured faster than the direct kernel by
+// more than the latter's run-to-run range (profiles/PERF_LOG.md, "Forward
+// GEMM operands through LDS"): at M = 8192, 256x512 8.6 against 21.4 us,
+// 512x368 13.0 against 19.6, 64x256 4.9 against 7.6. K = 16 and 64 and
+// N = 1 measured equal within that range, so they, and K % 8 != 0, which
+// the LDS kernel does not serve, keep the direct MT=1 kernel.
+static bool fwd_lds_is_faster(int64_t N, int64_t K) {
+  return K % 8 == 0 && K >= 256 && N >= 64;
+}
+
+torch::Tensor linear_fwd(torch::Tensor x, torch::Tensor w_bf16,
+                         torch::Tensor bias, int64_t act,
+                         int64_t variant) {
+  check_fwd_operands("linear_fwd", x, w_bf16, bias);
+  TORCH_CHECK(variant >= -1 && variant <= 1, "linear_fwd: variant must be "
+              "-1 (automatic), 0 (MT=1) or 1 (MT=2), got ", variant);
+  FwdKernel kernel = variant == 1 ? FwdKernel::MT2 : FwdKernel::MT1;
+  if (variant == -1 && fwd_lds_is_faster(w_bf16.size(0), x.size(1)))
+    kernel = FwdKernel::LDS;
+  return linear_fwd_launch(kernel, x, w_bf16, bias, act);
+}
+
+// k_linear_fwd_lds whatever the shape, for tests and tools/gemm_sweep.py
+torch::Tensor linear_fwd_lds(torch::Tensor x, torch::Tensor w_bf16,
+                             torch::Tensor bias, int64_t act) {
+  check_fwd_operands("linear_fwd_lds", x, w_bf16, bias);
+  TORCH_CHECK(x.size(1) % 8 == 0, "linear_fwd_lds: x is [M, K] with K = ",
+              x.size(1), "; K must be a multiple of 8");
+  return linear_fwd_launch(FwdKernel::LDS, x, w_bf16, bias, act);
 }
 
 // prev_out/prev_act: fuse the previous layer's activation gradient into
@@ -1423,6 +1615,8 @@ void register_dense(py::module_& mod) {
           py::arg("bot"), py::arg("emb"), py::arg("variant") = 0);
   mod.def("linear_fwd", &linear_fwd, py::arg("x"), py::arg("w"),
           py::arg("bias"), py::arg("act"), py::arg("variant") = -1);
+  mod.def("linear_fwd_lds", &linear_fwd_lds, py::arg("x"), py::arg("w"),
+          py::arg("bias"), py::arg("act"));
   mod.def("linear_dx", &linear_dx, py::arg("g"), py::arg("w"),
           py::arg("prev_out") = py::none(), py::arg("prev_act") = 0);
   mod.def("linear_dw", &linear_dw, py::arg("g"), py::arg("x"),

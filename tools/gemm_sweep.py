@@ -1,6 +1,7 @@
 """Per-shape microbenchmark of the fused-MLP kernels.
 
-Times linear_fwd / linear_dx / linear_dw on each DLRM layer shape, and on
+Times linear_fwd / linear_fwd_lds / linear_dx / linear_dw on each DLRM
+layer shape, and on
 the model-zoo shapes the same kernels serve, with hipEvents: eager loops
 of `--iters` calls, median of `--loops` loops, spread = max - min of the
 loops. The loops include the bindings' allocation and zero-fill and bottom
@@ -55,7 +56,7 @@ def main():
     args = p.parse_args()
     ext = require_extension()
     dev = torch.device("cuda")
-    names = ("fwd0", "fwd1", "dx", "dw16", "dw64t")
+    names = ("fwd0", "fwd1", "fwdlds", "dx", "dw16", "dw64t")
     print(f"{'M':>6} {'N':>4} {'K':>4} | "
           + " ".join(f"{n:>12}" for n in names) + "  us (spread)")
     tot = [0.0] * len(names)
@@ -66,14 +67,19 @@ def main():
         G = torch.randn(M, N, device=dev, dtype=torch.bfloat16)
         fns = (lambda: ext.linear_fwd(A, W, b, 1, 0),
                lambda: ext.linear_fwd(A, W, b, 1, 1),
+               # the LDS-staged kernel serves K % 8 == 0 only
+               (lambda: ext.linear_fwd_lds(A, W, b, 1)) if K % 8 == 0
+               else None,
                lambda: ext.linear_dx(G, W),
                lambda: ext.linear_dw(G, A, True, 0),
                lambda: ext.linear_dw(G, A, True, 2))
-        res = [time_fn(fn, args.iters, args.loops) for fn in fns]
+        res = [time_fn(fn, args.iters, args.loops) if fn else None
+               for fn in fns]
         print(f"{M:>6} {N:>4} {K:>4} | "
-              + " ".join(f"{m:7.1f}({s:3.1f})" for m, s in res))
-        for i, (m, _) in enumerate(res):
-            tot[i] += m
+              + " ".join(f"{r[0]:7.1f}({r[1]:3.1f})" if r else f"{'-':>12}"
+                         for r in res))
+        for i, r in enumerate(res):
+            tot[i] += r[0] if r else 0.0
     print(f"{'TOTAL':>16} | " + " ".join(f"{t:12.1f}" for t in tot))
 
 
