@@ -200,10 +200,10 @@ __global__ void k_insert_bulk(
 // ---------------------------------------------------------------------
 // fused hash dedup — replaces sort-based unique on the training hot path
 // ---------------------------------------------------------------------
-// The hash table itself deduplicates: pass A runs once per OCCURRENCE,
-// inserting the key if absent and claiming a compact index [0, m) for the
-// first toucher of this epoch (atomicExch on a per-entry epoch stamp —
-// exactly one winner). Pass C (per occurrence) reads back inverse indices
+// The hash table itself deduplicates: pass A covers every OCCURRENCE (one
+// probe per distinct key of a wave), inserting the key if absent and
+// claiming a compact index [0, m) for the first toucher of this epoch
+// (atomicExch on a per-entry epoch stamp — exactly one winner). Pass C (per occurrence) reads back inverse indices
 // and exact per-batch counts. Pass B (per unique key) applies the
 // frequency/version bookkeeping, admission + default-value init.
 // Equivalent outputs to torch.unique(return_inverse, return_counts) + the
@@ -216,10 +216,68 @@ __global__ void k_insert_bulk(
 // the captured step, so replays keep deduplicating correctly with zero
 // host involvement).
 
+// Wave-level grouping of equal values: zipf-hot keys put many equal keys
+// into one wave (the hottest DLRM key fills ~19 of 64 lanes of every wave
+// of its table), and per-occurrence atomics on them form one serial chain
+// per key. Passes A and C merge a wave's duplicates in registers and let
+// one leader lane per distinct value touch memory.
+struct WaveGroup {
+  uint64_t mask;  // valid lanes of this wave holding the same value
+  int leader;     // lowest lane of mask
+  int pos;        // this lane's position inside mask
+};
+
+// Registers only (ballots and one shuffle per 8 rounds, no memory
+// operation). Must be called by the WHOLE wave, converged; lanes with
+// valid == false get mask 0 / leader 0 / pos 0.
+//
+// One ballot per value BIT splits the lanes into classes agreeing on the
+// bits seen so far. Classes only ever split, and equal values share every
+// bit, so as soon as every lane equals the lowest lane of its class the
+// classes are exactly the groups of equal values. With values whose low
+// bits are spread (hash-table entries, key hashes) that holds after ~2*log2(64) bits
+// whether the wave holds 64 distinct values or one hot one; a loop that
+// retires one distinct value per round needs 64 rounds on all-distinct
+// input, which doubled pass C's time there.
+DEV_INLINE WaveGroup wave_group_by(uint64_t v, bool valid) {
+  WaveGroup g{0ull, 0, 0};
+  const int lane = __lane_id();
+  uint64_t mask = __ballot(valid);
+  int leader = lane;
+  for (int b = 0; b < 64; b += 8) {  // wave-uniform trip count
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const bool bit = (v >> (b + i)) & 1ull;
+      const uint64_t with = __ballot(bit);
+      mask &= bit ? with : ~with;  // a valid lane always keeps its own bit
+    }
+    leader = valid ? __ffsll((unsigned long long)mask) - 1 : lane;
+    const uint64_t lv = __shfl(v, leader);
+    if (!__ballot(valid && lv != v)) break;  // every class is one value
+  }
+  if (valid) {
+    g.mask = mask;
+    g.leader = leader;
+    g.pos = __popcll(mask & ((1ull << lane) - 1ull));
+  }
+  return g;
+}
+
+// First element of this wave's 64-wide slice and the grid's slice stride,
+// both wave-uniform, so a caller's grid-stride loop keeps every lane of the
+// wave in the loop (tail lanes are predicated, never exit early).
+DEV_INLINE int64_t wave_slice_begin() {
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  return (blockIdx.x * (int64_t)(blockDim.x >> 6) + wave) * 64;
+}
+DEV_INLINE int64_t wave_slice_stride() {
+  return gridDim.x * (int64_t)(blockDim.x >> 6) * 64;
+}
+
 // SKIP_PAD (the padded sequence lookup): a PAD_KEY occurrence is not a key
 // at all — no probe, no claim, no table entry; it records entry -1 for
-// pass C (which skips it by key) and moves on. One body for both
-// instantiations, so the claim logic cannot drift.
+// pass C (which skips it by key) and takes no part in the wave's grouping.
+// One body for all instantiations, so the claim logic cannot drift.
 //
 // MATRIX (the one-id-per-table layout): `keys` is the id matrix
 // ids[batch, n_tables] itself, row-major, and occurrence j = t * batch + b
@@ -237,43 +295,60 @@ __global__ void k_dedup_pass_a(
     int64_t* __restrict__ occ_entry, int32_t* __restrict__ error_flag,
     int batch = 0, int n_tables = 0, int key_bits = 0) {
   const int epoch = epoch_dev ? *epoch_dev : epoch_val;
-  int64_t j = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
-  int64_t stride = gridDim.x * (int64_t)blockDim.x;
-  for (; j < nnz; j += stride) {
-    int64_t key;
-    if constexpr (MATRIX) {
-      const int t = (int)j / batch;
-      const int b = (int)j - t * batch;
-      key = keys[(int64_t)b * n_tables + t] + ((int64_t)t << key_bits);
-    } else {
-      key = keys[j];
-    }
-    if constexpr (SKIP_PAD) {
-      if (key == PAD_KEY) {
-        occ_entry[j] = -1;
-        continue;
+  const int lane = __lane_id();
+  const int64_t stride = wave_slice_stride();
+  for (int64_t j0 = wave_slice_begin(); j0 < nnz; j0 += stride) {
+    const int64_t j = j0 + lane;
+    bool valid = j < nnz;
+    int64_t key = 0;
+    if (valid) {
+      if constexpr (MATRIX) {
+        const int t = (int)j / batch;
+        const int b = (int)j - t * batch;
+        key = keys[(int64_t)b * n_tables + t] + ((int64_t)t << key_bits);
+      } else {
+        key = keys[j];
+      }
+      if constexpr (SKIP_PAD) {
+        if (key == PAD_KEY) {
+          occ_entry[j] = -1;
+          valid = false;
+        }
       }
     }
-    int64_t idx = ht_find_or_claim(ht_keys, cap_mask, key, entry_counter);
-    if (idx < 0) {
-      atomicExch(error_flag, 2);
-      continue;
-    }
-    // freq/version updates live in pass B (one per UNIQUE key via pass
-    // C's exact counts): hot keys were serializing thousands of
-    // per-occurrence atomics on one cache line here. The plain read
-    // short-circuits the epoch claim for already-claimed keys; racing
-    // first-touchers are resolved by the atomicExch.
-    if (ht_epoch[idx] != epoch) {
-      int old = atomicExch(&ht_epoch[idx], epoch);
-      if (old != epoch) {  // first toucher this step
-        int c = atomicAdd(m_counter, 1);
-        ht_compact[idx] = c;
-        uniq_keys[c] = key;
-        compact_entry[c] = idx;
+    // The kernel's time is its random probes of the table, so a wave's
+    // occurrences of one key share ONE probe and one claim. Grouped on the
+    // key's hash, not on the key: mix_hash is a bijection on 64 bits (an
+    // add, two xorshift-multiplies by odd constants, an xorshift — each
+    // invertible), so equal hash means equal key exactly, and its low bits
+    // are spread, which is what lets wave_group_by finish in ~16 rounds.
+    // Raw composite keys (small zipf ids under a table tag in bit 48) are
+    // not spread.
+    const WaveGroup g = wave_group_by(mix_hash((uint64_t)key), valid);
+    int64_t idx = -1;
+    if (valid && lane == g.leader) {
+      idx = ht_find_or_claim(ht_keys, cap_mask, key, entry_counter);
+      if (idx < 0) {
+        atomicExch(error_flag, 2);
+      } else if (ht_epoch[idx] != epoch) {
+        // freq/version updates live in pass B (one per UNIQUE key via pass
+        // C's exact counts): hot keys were serializing thousands of
+        // per-occurrence atomics on one cache line here. The plain read
+        // short-circuits the epoch claim for already-claimed keys; racing
+        // first-touchers (leaders of other waves) are resolved by the
+        // atomicExch.
+        int old = atomicExch(&ht_epoch[idx], epoch);
+        if (old != epoch) {  // first toucher this step
+          int c = atomicAdd(m_counter, 1);
+          ht_compact[idx] = c;
+          uniq_keys[c] = key;
+          compact_entry[c] = idx;
+        }
       }
     }
-    occ_entry[j] = idx;  // pass C reads compact ids WITHOUT re-probing
+    idx = __shfl(idx, g.leader);
+    // pass C reads compact ids WITHOUT re-probing
+    if (valid && idx >= 0) occ_entry[j] = idx;
   }
 }
 
@@ -531,64 +606,6 @@ __global__ void k_rows_to_padded(const float* __restrict__ src,
     int d = (int)(t % dim);
     dst[(int64_t)route_pos[u] * dim + d] = src[t];
   }
-}
-
-// Wave-level grouping of equal values: zipf-hot keys put many equal keys
-// into one wave (the hottest DLRM key fills ~19 of 64 lanes of every wave
-// of its table), and per-occurrence atomics on them form one serial chain
-// per key. Pass C merges a wave's duplicates in registers and lets one
-// leader lane per distinct value touch memory.
-struct WaveGroup {
-  uint64_t mask;  // valid lanes of this wave holding the same value
-  int leader;     // lowest lane of mask
-  int pos;        // this lane's position inside mask
-};
-
-// Registers only (ballots and one shuffle per 8 rounds, no memory
-// operation). Must be called by the WHOLE wave, converged; lanes with
-// valid == false get mask 0 / leader 0 / pos 0.
-//
-// One ballot per value BIT splits the lanes into classes agreeing on the
-// bits seen so far. Classes only ever split, and equal values share every
-// bit, so as soon as every lane equals the lowest lane of its class the
-// classes are exactly the groups of equal values. With values whose low
-// bits are spread (hash-table entries) that holds after ~2*log2(64) bits
-// whether the wave holds 64 distinct values or one hot one; a loop that
-// retires one distinct value per round needs 64 rounds on all-distinct
-// input, which doubled pass C's time there.
-DEV_INLINE WaveGroup wave_group_by(uint64_t v, bool valid) {
-  WaveGroup g{0ull, 0, 0};
-  const int lane = __lane_id();
-  uint64_t mask = __ballot(valid);
-  int leader = lane;
-  for (int b = 0; b < 64; b += 8) {  // wave-uniform trip count
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-      const bool bit = (v >> (b + i)) & 1ull;
-      const uint64_t with = __ballot(bit);
-      mask &= bit ? with : ~with;  // a valid lane always keeps its own bit
-    }
-    leader = valid ? __ffsll((unsigned long long)mask) - 1 : lane;
-    const uint64_t lv = __shfl(v, leader);
-    if (!__ballot(valid && lv != v)) break;  // every class is one value
-  }
-  if (valid) {
-    g.mask = mask;
-    g.leader = leader;
-    g.pos = __popcll(mask & ((1ull << lane) - 1ull));
-  }
-  return g;
-}
-
-// First element of this wave's 64-wide slice and the grid's slice stride,
-// both wave-uniform, so a caller's grid-stride loop keeps every lane of the
-// wave in the loop (tail lanes are predicated, never exit early).
-DEV_INLINE int64_t wave_slice_begin() {
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  return (blockIdx.x * (int64_t)(blockDim.x >> 6) + wave) * 64;
-}
-DEV_INLINE int64_t wave_slice_stride() {
-  return gridDim.x * (int64_t)(blockDim.x >> 6) * 64;
 }
 
 // Pass C (per occurrence): inverse + exact per-batch counts. Index-direct:
