@@ -223,3 +223,71 @@ def masked_softmax_pool(scores: torch.Tensor, seq: torch.Tensor,
     e = torch.exp(s) * valid.to(s.dtype)
     w = e / (e.sum(dim=1, keepdim=True) + 1e-20)
     return (w.unsqueeze(2) * seq.float()).sum(1)
+
+
+# what din_attn_fwd / din_attn_bwd take (din_attention_kernels.hip)
+DIN_ATT_MAX_D, DIN_ATT_MAX_H, DIN_ATT_MAX_T = 64, 128, 1024
+
+
+def din_attention_workgroups(batch: int) -> int:
+    """Workgroups the din_attention kernels launch for `batch` samples."""
+    from deeprec_amd.ops.build_ext import require_extension
+    return require_extension().din_attn_grid(batch)
+
+
+class _DinAttention(torch.autograd.Function):
+    """DIN's activation unit and pooling as one node: features, both
+    linear layers, the masked softmax and the pooling in one kernel per
+    direction. Saves the softmax weights only."""
+
+    @staticmethod
+    def forward(ctx, seq, tgt, mask_u8, w1, b1, w2, b2, w16_1, w16_2,
+                ws1, ws2):
+        from deeprec_amd.ops.build_ext import require_extension
+        ext = require_extension()
+        w1_16 = (w16_1 if w16_1 is not None
+                 else w1.detach().to(torch.bfloat16).contiguous())
+        w2_16 = (w16_2 if w16_2 is not None
+                 else w2.detach().to(torch.bfloat16).contiguous()).view(-1)
+        b1f = b1.detach().float()
+        out, w = ext.din_attn_fwd(seq, tgt, mask_u8, w1_16, b1f, w2_16)
+        ctx.ext = ext
+        ctx.ws = (ws1, ws2)
+        ctx.save_for_backward(seq, tgt, mask_u8, w, w1_16, b1f, w2_16)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        seq, tgt, mask_u8, w, w1_16, b1f, w2_16 = ctx.saved_tensors
+        dseq, dtgt, dw1, db1, dw2, db2 = ctx.ext.din_attn_bwd(
+            dout.float().contiguous(), seq, tgt, mask_u8, w, w1_16, b1f,
+            w2_16, ctx.ws[0], ctx.ws[1])
+        return (dseq, dtgt, None, dw1, db1, dw2.view(1, -1), db2, None, None,
+                None, None)
+
+
+def din_attention(seq: torch.Tensor, tgt: torch.Tensor, mask: torch.Tensor,
+                  lin1: FusedLinear, lin2: FusedLinear) -> torch.Tensor:
+    """DIN's local-activation attention: softmax over the valid positions
+    of lin2(lin1([s, t, s-t, s*t])) pooling seq. seq [B,T,D], tgt [B,D],
+    mask [B,T] bool (True = valid), lin1 = FusedLinear(4D -> H, sigmoid),
+    lin2 = FusedLinear(H -> 1). On the GPU, within the kernels' limits
+    (D % 8 == 0 in [8, 64], H % 16 == 0 in [16, 128], T in [1, 1024]), one
+    fused node; anything else is the composition din_att_features -> lin1
+    -> lin2 -> masked_softmax_pool. A fully masked sample pools to zeros."""
+    b, t, d = seq.shape
+    h = lin1.out_features
+    if (seq.device.type == "cuda" and b > 0
+            and d % 8 == 0 and 8 <= d <= DIN_ATT_MAX_D
+            and h % 16 == 0 and 16 <= h <= DIN_ATT_MAX_H
+            and 1 <= t <= DIN_ATT_MAX_T
+            and lin1.in_features == 4 * d and lin1.activation == "sigmoid"
+            and lin2.in_features == h and lin2.out_features == 1
+            and lin2.activation in (None, "none")):
+        return _DinAttention.apply(
+            seq.float().contiguous(), tgt.float().contiguous(),
+            mask.to(torch.uint8).contiguous(), lin1.weight, lin1.bias,
+            lin2.weight, lin2.bias, lin1.w16_cache, lin2.w16_cache,
+            lin1.dw_ws, lin2.dw_ws)
+    scores = lin2(lin1(din_att_features(seq, tgt))).float().reshape(b, t)
+    return masked_softmax_pool(scores, seq, mask)

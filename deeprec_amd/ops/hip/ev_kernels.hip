@@ -1619,6 +1619,8 @@ void register_loss(pybind11::module_& mod);       // loss_kernels.hip
 void register_cross(pybind11::module_& mod);      // cross_kernels.hip
 void register_moe(pybind11::module_& mod);        // moe_kernels.hip
 void register_mask(pybind11::module_& mod);       // mask_kernels.hip
+// din_attention_kernels.hip
+void register_din_attention(pybind11::module_& mod);
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_dense(mod);
@@ -1631,6 +1633,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_cross(mod);
   register_moe(mod);
   register_mask(mod);
+  register_din_attention(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);

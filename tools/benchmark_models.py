@@ -4,7 +4,7 @@ device and writes a markdown table.
 
 Usage: python tools/benchmark_models.py [--steps 30] [--out profiles/...]
        [--static-seq] [--no-graph] [--fused-experts] [--fused-cross-train]
-       [--fused-mask-blocks]
+       [--fused-mask-blocks] [--fused-din-attention]
 --static-seq builds din/dien/bst with static_seq=True (one padded lookup
 for sequence and target); din and bst then train as a captured hipGraph
 like the dense-feature models. dien stays eager: its auxiliary loss draws a
@@ -18,6 +18,9 @@ mlperf_dlrm_dcn+fused, and they step eagerly: that node has not been run
 under graph capture.
 --fused-mask-blocks builds masknet with fused_blocks=True (mask-block
 kernels, ops/fused_mask.py); its row is then named masknet+fused.
+--fused-din-attention builds din with fused_attention=True (the activation
+unit as one node on the din_attention kernels, ops/fused_attention.py); its
+row is then named din+fused.
 Batch sizes follow the reference GPU benchmark config
 (modelzoo/benchmark/gpu/config.yaml: dlrm 8192, wide_and_deep 32768,
 deepfm 8192, dien 16384).
@@ -52,11 +55,13 @@ CAPTURABLE_SEQ = {"din", "bst"}
 FUSED_EXPERT_MODELS = {"mmoe", "ple"}
 FUSED_CROSS_MODELS = {"dcnv2", "mlperf_dlrm_dcn"}
 FUSED_MASK_MODELS = {"masknet"}
+FUSED_DIN_MODELS = {"din"}
 
 
 def bench_model(name, steps, warmup, device, use_graph=True,
                 static_seq=False, fused_experts=False,
-                fused_cross_train=False, fused_mask_blocks=False):
+                fused_cross_train=False, fused_mask_blocks=False,
+                fused_din_attention=False):
     from deeprec_amd.data.synthetic import CriteoSyntheticDataset
     from deeprec_amd.embedding.options import EmbeddingVariableOption
     from deeprec_amd.models import MODEL_REGISTRY, SEQUENCE_MODELS
@@ -78,6 +83,8 @@ def bench_model(name, steps, warmup, device, use_graph=True,
         kw["fused_cross_train"] = True
     if fused_mask_blocks and name in FUSED_MASK_MODELS:
         kw["fused_blocks"] = True
+    if fused_din_attention and name in FUSED_DIN_MODELS:
+        kw["fused_attention"] = True
     if use_graph:
         kw["ev_option"] = EmbeddingVariableOption(init_capacity=1 << 23)
     m = MODEL_REGISTRY[name](device=device, bf16=device.type == "cuda",
@@ -167,6 +174,9 @@ def main():
     p.add_argument("--fused-mask-blocks", action="store_true",
                    help="masknet runs its mask generators and blocks on "
                         "the MFMA linear and mask-block kernels")
+    p.add_argument("--fused-din-attention", action="store_true",
+                   help="din runs its activation unit and pooling on the "
+                        "din_attention kernels")
     p.add_argument("--no-graph", action="store_true",
                    help="step eagerly even where capture is possible")
     args = p.parse_args()
@@ -186,12 +196,16 @@ def main():
                                          fused_cross_train=args
                                          .fused_cross_train,
                                          fused_mask_blocks=args
-                                         .fused_mask_blocks)
+                                         .fused_mask_blocks,
+                                         fused_din_attention=args
+                                         .fused_din_attention)
             if (args.fused_experts and name in FUSED_EXPERT_MODELS
                     or args.fused_cross_train
                     and name in FUSED_CROSS_MODELS
                     or args.fused_mask_blocks
-                    and name in FUSED_MASK_MODELS):
+                    and name in FUSED_MASK_MODELS
+                    or args.fused_din_attention
+                    and name in FUSED_DIN_MODELS):
                 name += "+fused"
             rows.append((name, batch, sps, ms))
             print(f"{name:18s} batch={batch:6d}  {sps:12.0f} samples/s  "
