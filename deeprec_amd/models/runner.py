@@ -116,6 +116,9 @@ def build_argparser():
     p.add_argument("--fused_mask_blocks", action="store_true",
                    help="masknet: run the mask generators and blocks on "
                         "the MFMA linear and mask-block kernels")
+    p.add_argument("--fused_dien_aux", action="store_true",
+                   help="dien: compute the auxiliary loss and its gradients "
+                        "on the dien_aux kernels")
     p.add_argument("--eval_steps", type=int, default=0,
                    help="after training, evaluate N batches (no inserts, "
                         "no training) and print loss/accuracy/AUC — the "
@@ -151,8 +154,8 @@ def make_ev_option(args) -> EmbeddingVariableOption:
 
 def width_kwargs(args) -> dict:
     """--gru_hidden / --item_dim / --fused_experts / --fused_cross_train /
-    --fused_mask_blocks as constructor keywords: only those given, and only
-    for a model whose constructor names them."""
+    --fused_mask_blocks / --fused_dien_aux as constructor keywords: only
+    those given, and only for a model whose constructor names them."""
     params = inspect.signature(MODEL_REGISTRY[args.model]).parameters
     kw = {}
     for name in ("gru_hidden", "item_dim"):
@@ -165,7 +168,8 @@ def width_kwargs(args) -> dict:
         kw[name] = value
     for name, key in (("fused_experts", "fused_experts"),
                       ("fused_cross_train", "fused_cross_train"),
-                      ("fused_mask_blocks", "fused_blocks")):
+                      ("fused_mask_blocks", "fused_blocks"),
+                      ("fused_dien_aux", "fused_aux_loss")):
         if not getattr(args, name):
             continue
         if key not in params:

@@ -166,9 +166,14 @@ class DIEN(_SeqBase):
 
     def __init__(self, embedding_dim=16, item_dim=32, gru_hidden=32,
                  att_hidden=64, mlp_sizes=(256, 128, 64), device="cpu",
-                 bf16=True, use_aux_loss=True, aux_alpha=1.0, **kw):
+                 bf16=True, use_aux_loss=True, aux_alpha=1.0,
+                 fused_aux_loss=False, **kw):
         super().__init__(embedding_dim, item_dim, device, bf16, name="dien",
                          **kw)
+        # fused_aux_loss: the auxiliary loss and all its gradients as one
+        # autograd node on the dien_aux kernels (bf16 operands, no host
+        # branch); same parameters and state_dict keys
+        self.fused_aux_loss = fused_aux_loss
         # auxiliary next-item supervision on the GRU hidden states
         # (reference: _auxiliary_loss, modelzoo/dien/train.py:231-251:
         # click pair [h_t; e_{t+1}] vs negative pair, masked log-loss
@@ -225,13 +230,27 @@ class DIEN(_SeqBase):
             out = self.mlp(x.to(self.compute_dtype))
         return out.float().squeeze(1)
 
-    def _auxiliary_loss(self, h_seq, seq, mask):
+    def _aux_is_plain(self):
+        """No hook has to fire on aux_net or one of its layers."""
+        from deeprec_amd.ops.fused_mlp import (_has_hooks,
+                                               _global_module_hooks)
+        return not (_has_hooks(self.aux_net)
+                    or any(_has_hooks(m) for m in self.aux_net)
+                    or _global_module_hooks())
+
+    def _auxiliary_loss(self, h_seq, seq, mask, perm=None):
         """Masked BCE over click pairs [h_t; e_{t+1}] vs no-click pairs
         [h_t; e_shuffled_{t+1}] (reference semantics; sigmoid+BCE is the
-        numerically-stable form of its softmax+log)."""
+        numerically-stable form of its softmax+log). perm: the in-batch
+        negatives' permutation, drawn here when None."""
+        if perm is None:
+            perm = torch.randperm(seq.shape[0], device=seq.device)
+        if self.fused_aux_loss and self.bf16 and self._aux_is_plain():
+            from deeprec_amd.ops.fused_aux_loss import dien_aux_loss
+            return dien_aux_loss(h_seq, seq, mask, perm, self.aux_net[0],
+                                 self.aux_net[2])
         h = h_seq[:, :-1].float()                        # [B,T-1,H]
         click = seq[:, 1:].float()                       # real next items
-        perm = torch.randperm(seq.shape[0], device=seq.device)
         noclick = click[perm]                            # in-batch negatives
         m = (mask[:, :-1] * mask[:, 1:])                 # both steps valid
         m = m * (perm != torch.arange(seq.shape[0],

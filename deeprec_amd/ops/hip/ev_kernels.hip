@@ -1621,6 +1621,7 @@ void register_moe(pybind11::module_& mod);        // moe_kernels.hip
 void register_mask(pybind11::module_& mod);       // mask_kernels.hip
 // din_attention_kernels.hip
 void register_din_attention(pybind11::module_& mod);
+void register_dien_aux(pybind11::module_& mod);   // dien_aux_kernels.hip
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_dense(mod);
@@ -1634,6 +1635,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, mod) {
   register_moe(mod);
   register_mask(mod);
   register_din_attention(mod);
+  register_dien_aux(mod);
   mod.def("ht_lookup_insert", &ht_lookup_insert);
   mod.def("ht_dedup_a", &ht_dedup_a);
   mod.def("ht_dedup_a_pad", &ht_dedup_a_pad);

@@ -4,7 +4,7 @@ device and writes a markdown table.
 
 Usage: python tools/benchmark_models.py [--steps 30] [--out profiles/...]
        [--static-seq] [--no-graph] [--fused-experts] [--fused-cross-train]
-       [--fused-mask-blocks] [--fused-din-attention]
+       [--fused-mask-blocks] [--fused-din-attention] [--fused-dien-aux]
 --static-seq builds din/dien/bst with static_seq=True (one padded lookup
 for sequence and target); din and bst then train as a captured hipGraph
 like the dense-feature models. dien stays eager: its auxiliary loss draws a
@@ -21,6 +21,9 @@ kernels, ops/fused_mask.py); its row is then named masknet+fused.
 --fused-din-attention builds din with fused_attention=True (the activation
 unit as one node on the din_attention kernels, ops/fused_attention.py); its
 row is then named din+fused.
+--fused-dien-aux builds dien with fused_aux_loss=True (the auxiliary loss as
+one node on the dien_aux kernels, ops/fused_aux_loss.py); its row is then
+named dien+fused.
 Batch sizes follow the reference GPU benchmark config
 (modelzoo/benchmark/gpu/config.yaml: dlrm 8192, wide_and_deep 32768,
 deepfm 8192, dien 16384).
@@ -56,12 +59,13 @@ FUSED_EXPERT_MODELS = {"mmoe", "ple"}
 FUSED_CROSS_MODELS = {"dcnv2", "mlperf_dlrm_dcn"}
 FUSED_MASK_MODELS = {"masknet"}
 FUSED_DIN_MODELS = {"din"}
+FUSED_DIEN_MODELS = {"dien"}
 
 
 def bench_model(name, steps, warmup, device, use_graph=True,
                 static_seq=False, fused_experts=False,
                 fused_cross_train=False, fused_mask_blocks=False,
-                fused_din_attention=False):
+                fused_din_attention=False, fused_dien_aux=False):
     from deeprec_amd.data.synthetic import CriteoSyntheticDataset
     from deeprec_amd.embedding.options import EmbeddingVariableOption
     from deeprec_amd.models import MODEL_REGISTRY, SEQUENCE_MODELS
@@ -85,6 +89,8 @@ def bench_model(name, steps, warmup, device, use_graph=True,
         kw["fused_blocks"] = True
     if fused_din_attention and name in FUSED_DIN_MODELS:
         kw["fused_attention"] = True
+    if fused_dien_aux and name in FUSED_DIEN_MODELS:
+        kw["fused_aux_loss"] = True
     if use_graph:
         kw["ev_option"] = EmbeddingVariableOption(init_capacity=1 << 23)
     m = MODEL_REGISTRY[name](device=device, bf16=device.type == "cuda",
@@ -177,6 +183,9 @@ def main():
     p.add_argument("--fused-din-attention", action="store_true",
                    help="din runs its activation unit and pooling on the "
                         "din_attention kernels")
+    p.add_argument("--fused-dien-aux", action="store_true",
+                   help="dien computes its auxiliary loss and gradients on "
+                        "the dien_aux kernels")
     p.add_argument("--no-graph", action="store_true",
                    help="step eagerly even where capture is possible")
     args = p.parse_args()
@@ -198,14 +207,17 @@ def main():
                                          fused_mask_blocks=args
                                          .fused_mask_blocks,
                                          fused_din_attention=args
-                                         .fused_din_attention)
+                                         .fused_din_attention,
+                                         fused_dien_aux=args.fused_dien_aux)
             if (args.fused_experts and name in FUSED_EXPERT_MODELS
                     or args.fused_cross_train
                     and name in FUSED_CROSS_MODELS
                     or args.fused_mask_blocks
                     and name in FUSED_MASK_MODELS
                     or args.fused_din_attention
-                    and name in FUSED_DIN_MODELS):
+                    and name in FUSED_DIN_MODELS
+                    or args.fused_dien_aux
+                    and name in FUSED_DIEN_MODELS):
                 name += "+fused"
             rows.append((name, batch, sps, ms))
             print(f"{name:18s} batch={batch:6d}  {sps:12.0f} samples/s  "
